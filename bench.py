@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training throughput of the self-supervised depth step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,24 @@ One step = BASELINE.json configs[1]: ResNet-18 depth encoder/decoder + separate 
 GPU, synthetic KITTI-shaped inputs resident in HBM.  Data parallel: one process per GPU, DDP over RCCL;
 per-GPU work is fixed (weak scaling).  Prints ONE JSON line on rank 0.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (images/s, ms_per_step).  --full adds the side
+measurements below: the roofline of the training kernel and of the network kernels, the DataLoader-fed trainer loop,
+the image-preparation cost and the CPU baseline (--no-roofline, --no-trainer-loop, --no-cpu-baseline leave some out).
+
+--dump-outputs DIR writes what the timed path's step returns to its caller (the step's outputs dictionary: loss,
+disparities, poses, depth, auto-mask indices, encoder features) as DIR/<name>.npy, float32 (float64 stays float64),
+64 MB at most in all: an array larger than its share holds a fixed, seeded sample of its elements (dump_outputs).
+After the timed steps the run goes back to the state it started from (start_state) and takes two more steps of the
+timed path, untimed; the second one's outputs are dumped.  They come from weights that one full training step --
+forward, backward with the photometric gradient, Adam -- has updated, so a build that gets any of these wrong dumps
+other arrays.  Not the last timed step itself: the networks' MIOpen convolutions add partial sums with atomics, so
+after W + K Adam steps two runs hold weights that differ far beyond rounding; over one step the difference stays
+small.  Inputs and start state are seeded, so two runs with the same arguments -- on two builds -- can be compared, with
+a tolerance: two runs of one build (also with other --steps / --warmup) differ by ~5e-6 relative in the loss, up to
+~6e-5 in the disparities and ~1.5e-4 in the encoder features (Adam's first update is lr * sign(gradient), and gradients
+within rounding of zero can flip), and at a few dozen of 1.47 M auto-mask indices per scale (near-ties of the argmin).
+
+Extra objects in the line (--full):
   roofline      the dominant hand-written kernel: mdx::photometric_train_kernel (all scales, forward + gradient, one
                 launch per step).  achieved = algorithmic bytes per launch (per scale, forward + backward
                 formula, summed over the scales one launch processes) / launch duration; the duration is the mean over
@@ -350,6 +367,75 @@ def network_kernel_roofline(args, opt):
     return out
 
 
+DUMP_BYTES = 64 * 1000 * 1000       # --dump-outputs: all arrays together, .npy headers included
+
+
+def start_state(tr):
+    """Everything a training step changes -- weights and buffers, Adam's moments and step counts, the in-kernel noise
+    generator's {seed, offset}, the batch-norm modules' pending counts, torch's generators -- saved now; the returned
+    function puts it back in place (a captured step keeps reading the same tensors).  Adam state that does not exist yet
+    is put back as Adam's initial state (zeros), as model_train.graphed_step does after its warm-up."""
+    from model_layer.depth_encoder import BatchNorm2d
+    nets = list(tr.setting.raw_model.values())
+    tensors = [t for net in nets for t in list(net.parameters()) + list(net.buffers())]
+    saved = [t.detach().clone() for t in tensors]
+    bns = [m for net in nets for m in net.modules() if isinstance(m, BatchNorm2d)]
+    pending = [m._pending_batches for m in bns]
+    optim = tr.setting.optim["optimizer"]
+    moments = {id(p): {k: v.detach().clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optim.state.items()}
+    rng = tr.compute.noise_rng() if tr.compute.draws_in_kernel() else None
+    rng_saved = rng.tensor.clone() if rng is not None else None
+    gens = (torch.get_rng_state(), torch.cuda.get_rng_state() if torch.cuda.is_available() else None)
+
+    def restore():
+        with torch.no_grad():
+            for t, v in zip(tensors, saved):
+                t.copy_(v)
+            for p, st in optim.state.items():
+                old = moments.get(id(p), {})
+                for k, v in st.items():
+                    if torch.is_tensor(v):
+                        v.copy_(old[k]) if k in old else v.zero_()
+            if rng is not None:
+                rng.tensor.copy_(rng_saved)
+        for m, n in zip(bns, pending):
+            m._pending_batches = n
+        torch.set_rng_state(gens[0])
+        if gens[1] is not None:
+            torch.cuda.set_rng_state(gens[1])
+    return restore
+
+
+def dump_outputs(outputs, path):
+    """The tensors of the step's outputs dictionary as path/<name>.npy: keys joined by "_" (("disp", 0) -> disp_0, a list
+    value -> one file per element), float32, or float64 where the step returned float64.  Smallest first, every array gets
+    an equal share of what is left of DUMP_BYTES; a larger one is stored flat as a sample of that many elements, taken at
+    the same sorted, seeded positions (of the logical, row-major order) in every run.  Returns (arrays, bytes) written."""
+    import re
+    arrays = {}
+    for key, v in outputs.items():
+        name = re.sub(r"[^A-Za-z0-9_.-]", "_", "_".join(str(p) for p in key) if isinstance(key, tuple) else str(key))
+        if torch.is_tensor(v):
+            arrays[name] = v
+        elif isinstance(v, (list, tuple)):
+            arrays.update(("%s_%d" % (name, i), t) for i, t in enumerate(v) if torch.is_tensor(t))
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    total = 0
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = (DUMP_BYTES - total) // (len(items) - i) // (8 if dt == torch.float64 else 4) - 64   # room for the .npy header
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dt).cpu().numpy()
+        f = os.path.join(path, name + ".npy")
+        np.save(f, a)
+        total += os.path.getsize(f)
+    return len(arrays), total
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -540,9 +626,19 @@ def main():
                     help="pose network AFTER the depth network instead of beside it on a side stream (A/B: model_option --overlap_pose 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, the side measurements too: roofline (training kernel + network kernels), trainer "
+                         "loop, image preparation, CPU baseline; without it the run times the resident step alone")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, take two more from the start state and write what the second returned as "
+                         "DIR/<name>.npy (float32, 64 MB at most in all)")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trainer-loop-child", type=str, default="", choices=["", "raw", "prepared"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_trainer_loop = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))        # nothing has touched the GPU yet
@@ -624,13 +720,15 @@ def main():
     inputs = one_batch(st, device)
 
     def step():
-        return tr._eager_step(inputs)["loss"]
+        return tr._eager_step(inputs)
 
     def fence():
         if distributed:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: the state the run starts from (seeded: identical in every run with the same arguments)
+    restore = start_state(tr) if args.dump_outputs else None
     graph = None
     if args.graph and not tr.can_graph():
         raise SystemExit("bench.py: --graph needs a capturable step (device-side noise, RCCL process group)")
@@ -643,7 +741,7 @@ def main():
             graph({})
 
         def run():
-            return graph({})["loss"]             # inputs stay where they are: replay only
+            return graph({})                     # inputs stay where they are: replay only
     else:
         run = step
         for _ in range(args.warmup):
@@ -656,10 +754,25 @@ def main():
     F.TIMING = timing
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = run()
+        outputs = run()
     fence()
     dt = time.perf_counter() - t0
     F.TIMING = None
+    loss_val = float(outputs["loss"].detach())
+    del outputs
+    if restore is not None:
+        # The step's MIOpen convolutions add partial sums with atomics: one step from one state differs from run to run in
+        # the last bits only, but W + K Adam steps compound that into differences far beyond rounding.  So: the timed path's
+        # step (the same captured graph, or the eager step) twice from the start state, the second one dumped -- its outputs
+        # depend on the first one's backward and Adam update.  Every rank takes them (they may contain the exchange).
+        restore()
+        run()
+        outputs = run()
+        fence()
+        if rank == 0:
+            n, nbytes = dump_outputs(outputs, args.dump_outputs)
+            sys.stderr.write("bench.py: %d arrays of the second step from the start state, %.1f MB, in %s\n" % (n, nbytes / 1e6, args.dump_outputs))
+        del outputs
     if not args.no_roofline and graph is not None:
         # graph replay launches no Python: time the kernels over a few eager steps after the timed region instead
         # (every rank: the eager step contains the exchange)
@@ -685,7 +798,6 @@ def main():
         ones = torch.ones(1, device=tdev)
         torch.distributed.all_reduce(ones)           # every rank really took part (RCCL when backend is nccl)
         ranks_verified = int(ones[0])
-    loss_val = float(loss.detach())
     failed = False
 
     line = None

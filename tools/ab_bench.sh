@@ -3,7 +3,7 @@
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 PK="$ROOT/digging-into-self-supervised-monocular-depth-estimation_amd"
 OUT="$ROOT/gpurun_out/abb"; mkdir -p "$OUT"; cd "$ROOT"
-run() { n=$1; lib=$2; shift 2; MDX_LIB="$lib" timeout -k 10 200 python bench.py --no-cpu-baseline --no-trainer-loop --steps 40 --warmup 10 "$@" > "$OUT/$n.json" 2> "$OUT/$n.err"; python - "$OUT/$n.json" "$n" <<'PY'
+run() { n=$1; lib=$2; shift 2; MDX_LIB="$lib" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-trainer-loop --steps 40 --warmup 10 "$@" > "$OUT/$n.json" 2> "$OUT/$n.err"; python - "$OUT/$n.json" "$n" <<'PY'
 import json,sys
 try:
     d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r=d["roofline"]

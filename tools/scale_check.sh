@@ -33,22 +33,22 @@ SECTIONS="${SECTIONS:-A B C D E}"
 run() { name=$1; shift; echo "== $name: $*"; "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "   rc=$? $(tail -c 400 "$OUT/$name.json" | tr '\n' ' ' | cut -c1-200)"; }
 for sec in $SECTIONS; do case $sec in
 A) for n in 1 2 4 8; do
-       run "A_fp32_split_n$n" python bench.py --gpus $n --steps 100 --warmup 20
-       run "A_bf16_split_n$n" python bench.py --gpus $n --steps 100 --warmup 20 --amp bf16
+       run "A_fp32_split_n$n" python bench.py --full --gpus $n --steps 100 --warmup 20
+       run "A_bf16_split_n$n" python bench.py --full --gpus $n --steps 100 --warmup 20 --amp bf16
    done
-   run "A_bf16_split_n8_comm_bf16" python bench.py --gpus 8 --steps 100 --warmup 20 --amp bf16 --grad-comm bf16 ;;
+   run "A_bf16_split_n8_comm_bf16" python bench.py --full --gpus 8 --steps 100 --warmup 20 --amp bf16 --grad-comm bf16 ;;
 B) for n in 2 4 8; do
-       MDX_DP_GRAPH=1 run "B_fp32_onegraph_n$n" python bench.py --gpus $n --steps 100 --warmup 20
-       MDX_DP_GRAPH=1 run "B_bf16_onegraph_n$n" python bench.py --gpus $n --steps 100 --warmup 20 --amp bf16
+       MDX_DP_GRAPH=1 run "B_fp32_onegraph_n$n" python bench.py --full --gpus $n --steps 100 --warmup 20
+       MDX_DP_GRAPH=1 run "B_bf16_onegraph_n$n" python bench.py --full --gpus $n --steps 100 --warmup 20 --amp bf16
    done ;;
 C) for q in 0 2 8; do
-       MDX_HW_QUEUES=$q run "C_bf16_split_n8_queues$q" python bench.py --gpus 8 --steps 60 --warmup 20 --amp bf16 --one-loop
+       MDX_HW_QUEUES=$q run "C_bf16_split_n8_queues$q" python bench.py --full --gpus 8 --steps 60 --warmup 20 --amp bf16 --one-loop
    done ;;
 D) run "D_loader_8ranks" python tools/loader_cost.py --ranks 8 --workers 24 --seconds 15
    run "D_loader_6ranks_pinned" python tools/loader_cost.py --ranks 6 --workers 24 --seconds 15 --pin 1 ;;
 E) for n in 1 8; do
-       run "E_fp32_eager_n$n" python bench.py --gpus $n --steps 100 --warmup 20 --eager
-       MDX_HW_QUEUES=8 run "E_fp32_eager_n${n}_queues8" python bench.py --gpus $n --steps 100 --warmup 20 --eager
+       run "E_fp32_eager_n$n" python bench.py --full --gpus $n --steps 100 --warmup 20 --eager
+       MDX_HW_QUEUES=8 run "E_fp32_eager_n${n}_queues8" python bench.py --full --gpus $n --steps 100 --warmup 20 --eager
    done ;;
 esac; done
 python - "$OUT" <<'PY'

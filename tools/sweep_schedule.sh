@@ -5,7 +5,7 @@ PK="$ROOT/digging-into-self-supervised-monocular-depth-estimation_amd"
 SCHEDULES="${SCHEDULES:-40,0.6,20,0.25,10 40,0.42,24,0.37,12}"
 OUT="$ROOT/gpurun_out/sweep"; mkdir -p "$OUT"; cd "$ROOT"
 for sch in $SCHEDULES; do
-    MDX_LIB="$PK/libmdx_ab_dev.so" MDX_TRAIN_SCHEDULE="$sch" timeout -k 10 200 python bench.py --no-cpu-baseline --no-trainer-loop --steps 40 --warmup 10 > "$OUT/s.json" 2> "$OUT/s.err"
+    MDX_LIB="$PK/libmdx_ab_dev.so" MDX_TRAIN_SCHEDULE="$sch" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-trainer-loop --steps 40 --warmup 10 > "$OUT/s.json" 2> "$OUT/s.err"
     python - "$OUT/s.json" "$sch" <<'PY'
 import json,sys
 try:
