@@ -51,9 +51,9 @@ def dp_graph_allowed(world):
     RCCL out of the capture: model_train.graphed_step.)  One rank: yes (measured and
     tested on the GPU: tests/test_gpu_driver.py).  Several ranks: only with MDX_DP_GRAPH=1 -- a captured MULTI-rank RCCL
     all-reduce (fork / join of the communicator's stream inside the capture, replay order across ranks) has not run on
-    hardware yet (no multi-GPU node was available to this build: SCALE_r01..r03 were skipped), so the default
-    data-parallel step is the eager one with 32 MB buckets overlapping backward.  tools/scale_check.sh holds the runs
-    that settle it."""
+    hardware yet (no multi-GPU node was available to this build: SCALE_r01..r05 were skipped), so the default
+    data-parallel step is the split capture (model_train.trainer.train_step with opt.graph, the default); the eager step with
+    32 MB buckets overlapping backward is what runs without a capture.  tools/scale_check.sh holds the runs that settle it."""
     return int(world) <= 1 or os.environ.get("MDX_DP_GRAPH", "") == "1"
 
 
@@ -123,19 +123,25 @@ class grad_sync(object):
                 self._views[id(p)] = grad_view(self.flat, self.offsets[id(p)], p)
         self._avg = self.backend == "nccl"                      # ncclAvg exists in RCCL; gloo only sums
         self._works = []
-        self._xs, self._streams = None, []                       # exchange stream; streams seen producing gradients
+        self._xs, self._streams = None, []                       # exchange stream; registered side streams of backward
+        self._backward_stream = None                             # the stream zero() ran on: backward() is called there
         self._reset()
         self.zero()
         self._hooks = [p.register_post_accumulate_grad_hook(self._ready) for p in self.params]
 
     def backward_streams(self, streams):
-        """Side streams on which parts of backward run (besides the stream backward() is called on): the exchange waits for them
-        too.  Static, so that the per-parameter hook stays as light as it can be (an eager data-parallel step is host-bound)."""
+        """Side streams on which parts of backward run besides the stream backward() is called on (which zero() records).  A
+        bucket's gather waits for all of them: the hook that completes a bucket may run on any one of them while another is still
+        writing gradients of that bucket.  Static, so that the per-parameter hook stays as light as it can be (an eager
+        data-parallel step is host-bound)."""
         self._streams = [t for t in streams if t is not None]
 
     def zero(self):
         """Instead of optimizer.zero_grad(): `.grad` = None, so backward's accumulation keeps the incoming tensor as
-        it is (no read-modify-write pass); the gather into the flat buffer overwrites, nothing needs clearing."""
+        it is (no read-modify-write pass); the gather into the flat buffer overwrites, nothing needs clearing.  Called right
+        before backward(), on the stream backward() is called on: every bucket's gather waits for that stream (_issue)."""
+        if self.flat.is_cuda:
+            self._backward_stream = torch.cuda.current_stream(self.flat.device)
         for p in self.params:
             p.grad = None
 
@@ -166,10 +172,17 @@ class grad_sync(object):
         # against 654 images/s without the overlap; stream-side waits on events are capturable).
         if self._xs is None:
             self._xs = torch.cuda.Stream(self.flat.device)
-        # everything the backward streams have been given so far, the bucket's gradients included: the stream this hook runs on and
-        # the ones the trainer registered (the pose network's backward runs beside the depth network's, model_train.trainer)
-        self._xs.wait_stream(torch.cuda.current_stream(self.flat.device))
-        for t in self._streams:
+        # everything the backward streams have been given so far, the bucket's gradients included: the stream backward() was
+        # called on (recorded by zero()), the stream this hook runs on and the side streams the trainer registered.  Waiting on
+        # the hook's stream alone is not enough: with the pose network beside the depth network (model_train.trainer) the pose
+        # network's nodes come earlier in the forward, so autograd runs them last and the hook that completes the last bucket
+        # fires on the pose stream while the depth network's first weight gradients may still be in flight on backward()'s
+        # stream (in a captured graph: no edge from them to the gather).  tests/test_gpu_grad_exchange.py
+        waits = [torch.cuda.current_stream(self.flat.device)]
+        for t in [self._backward_stream] + self._streams:
+            if t is not None and all(t != w for w in waits):
+                waits.append(t)
+        for t in waits:
             self._xs.wait_stream(t)
         with torch.cuda.stream(self._xs):
             self._issue_on_current(k)

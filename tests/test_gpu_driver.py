@@ -241,7 +241,8 @@ def test_kitti_tree_training_and_eigen_style_evaluation(G, tmp_path):
 
 
 def _trainer_losses(graph, automask=False, noise="device", n=6, lr_change_at=4, amp="none", channels_last="auto", batches=None,
-                    frame_ids=(0, -1, 1), overlap_pose=True, shadow_weights=True):
+                    frame_ids=(0, -1, 1), overlap_pose=True, shadow_weights=True, on_build=None, on_step=None):
+    """`on_build(tr)` runs once the trainer is built, before its first step; `on_step(i, tr)` after step i."""
     import importlib
     bench = importlib.import_module("bench")
     from model_train import trainer
@@ -254,6 +255,8 @@ def _trainer_losses(graph, automask=False, noise="device", n=6, lr_change_at=4, 
     if batches is None:
         batches = list(tr.setting.train_dataloader)[:n]
     tr.last_batches = batches
+    if on_build is not None:
+        on_build(tr)
     torch.manual_seed(1)
     losses = []
     for i, b in enumerate(batches):
@@ -264,6 +267,8 @@ def _trainer_losses(graph, automask=False, noise="device", n=6, lr_change_at=4, 
                 else:
                     g["lr"] = 1e-6
         losses.append(float(tr.train_step(dict(b))["loss"].detach()))
+        if on_step is not None:
+            on_step(i, tr)
     enc = tr.setting.raw_model["encoder"]
     return losses, int(enc.state_dict()["encoder.bn1.num_batches_tracked"]), tr
 

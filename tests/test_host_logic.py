@@ -297,3 +297,39 @@ def test_checkpoint_resume_restores_weights_optimizer_and_schedule(tmp_path, mon
             assert torch.allclose(a, b, rtol=0, atol=1e-7), (key, n)
     with pytest.raises(FileNotFoundError):
         ct2.resume(st2, 3)
+
+
+def test_grad_sync_gather_waits_for_the_stream_backward_runs_on(monkeypatch):
+    """The hook that completes a bucket may run on a side stream (the pose network's backward beside the depth network's,
+    model_train.trainer) while the stream backward() was called on still writes that bucket's gradients: grad_sync._issue
+    makes the exchange stream wait for the stream zero() ran on, the hook's stream and the registered side streams.  Stand-in
+    streams, no GPU (tests/test_gpu_grad_exchange.py checks the gradients themselves on one)."""
+    import contextlib
+    from model_tool import parallel
+
+    class _Stream(object):
+        def __init__(self, name):
+            self.name, self.waited = name, []
+
+        def wait_stream(self, other):
+            self.waited.append(other.name)
+
+    main, pose, side, xs = _Stream("main"), _Stream("pose"), _Stream("side"), _Stream("exchange")
+    current = [main]
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: current[0])
+    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: xs)
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
+    sync = object.__new__(parallel.grad_sync)          # the stream logic alone: no process group, no buffers
+    sync.flat = types.SimpleNamespace(is_cuda=True, device="cuda:0")
+    sync.params, sync._xs, sync._streams = [], None, []
+    issued = []
+    sync._issue_on_current = lambda k: issued.append((k, sorted(xs.waited)))
+    sync.backward_streams([pose, side])
+    sync.zero()                                        # right before backward(), on its stream
+    current[0] = pose                                  # the last bucket's hook runs on the pose stream
+    sync._issue(0)
+    current[0] = main                                  # finish(): what no hook issued, on backward()'s stream
+    xs.waited = []
+    sync._issue(1)
+    assert issued == [(0, ["main", "pose", "side"]), (1, ["main", "pose", "side"])], issued
+    assert main.waited == pose.waited == side.waited == []     # the backward streams never wait (for each other or the gather)
