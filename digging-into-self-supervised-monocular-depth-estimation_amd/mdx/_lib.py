@@ -1,24 +1,56 @@
 """ctypes binding of libmdx_hip.so (include/mdx.h).  No torch types cross this boundary: tensors are
 handed over as raw device pointers + sizes, the current HIP stream as a void*.
 
+The binding is read from the header alone: its prototypes give every entry point's argtypes / restype, its #defines the
+constants below.  Call through `api` (checked); `lib()` is the typed raw handle, for callers that want a status code.
+
 There is NO fallback: if the library is missing or a tensor is not a contiguous float32 CUDA/HIP
 tensor, the call raises.
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
-LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                     "libmdx_hip.so")   # MDX_LIB: developer override (kernel A/B builds)
-MAX_SRC = 4
-MAX_SCALES = 4
-FLAG_AUTOMASK = 1
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_PKG, "libmdx_hip.so")   # MDX_LIB: developer override (kernel A/B builds)
+HEADER = os.path.join(os.path.dirname(_PKG), "include", "mdx.h")
 _lib = None
 
 
 class MdxError(RuntimeError):
     pass
+
+
+with open(HEADER) as _f:
+    _HEADER_TEXT = _f.read()
+DEFINES = {k: int(v) for k, v in re.findall(r"^#define\s+MDX_(\w+)\s+(\d+)u?\b", _HEADER_TEXT, re.M)}
+MAX_SRC, MAX_SCALES, FLAG_AUTOMASK = DEFINES["MAX_SRC"], DEFINES["MAX_SCALES"], DEFINES["FLAG_AUTOMASK"]
+
+# C types of the prototypes -> ctypes.  Every pointer parameter is a c_void_p: it takes ptr()'s c_void_p, C.byref(struct),
+# ctypes arrays, None and plain integers.
+_ARGTYPES = {"int": C.c_int, "size_t": C.c_size_t, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_RESTYPES = {"int": C.c_int, "size_t": C.c_size_t, "void": None, "void *": C.c_void_p, "const char *": C.c_char_p}
+
+
+def _ctype(table, decl, entry):
+    t = " ".join(decl.replace("*", " * ").split())
+    if table is _ARGTYPES and "*" in t:
+        return C.c_void_p
+    if t not in table:
+        raise MdxError("include/mdx.h: %s has a parameter or result of type '%s', which the binding does not map" % (entry, t))
+    return table[t]
+
+
+def signatures():
+    """{entry point: (restype, [argtypes])} for every prototype of include/mdx.h."""
+    code = re.sub(r"^\s*#.*$", "", re.sub(r"/\*.*?\*/", "", _HEADER_TEXT, flags=re.S), flags=re.M)
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(mdx_\w+)\s*\(([^()]*)\)\s*;", code):
+        params = [] if params.strip() == "void" else [re.sub(r"\w+\s*$", "", p) for p in params.split(",")]
+        sigs[name] = (_ctype(_RESTYPES, ret, name), [_ctype(_ARGTYPES, p, name) for p in params])
+    return sigs
 
 
 class Desc(C.Structure):
@@ -40,47 +72,35 @@ class Timing(C.Structure):   # mdx_timing: hipEvent_t pair recorded right before
     _fields_ = [("start", C.c_void_p), ("stop", C.c_void_p)]
 
 
-# every symbol include/mdx.h declares: name -> restype (None = int status)
-SYMBOLS = {
-    "mdx_version": C.c_int, "mdx_status_string": C.c_char_p, "mdx_desc_init": C.c_int,
-    "mdx_compose_projection": C.c_int, "mdx_identity_loss": C.c_int,
-    "mdx_photometric_workspace_bytes": C.c_size_t, "mdx_photometric_fwd": C.c_int,
-    "mdx_photometric_bwd": C.c_int, "mdx_smooth_workspace_bytes": C.c_size_t, "mdx_smooth_loss": C.c_int,
-    "mdx_interpolate_bilinear_fwd": C.c_int, "mdx_interpolate_bilinear_bwd": C.c_int,
-    "mdx_disparity2depth_fwd": C.c_int, "mdx_disparity2depth_bwd": C.c_int,
-    "mdx_backproject_fwd": C.c_int, "mdx_backproject_bwd": C.c_int,
-    "mdx_project_workspace_bytes": C.c_size_t, "mdx_project_fwd": C.c_int, "mdx_project_bwd": C.c_int,
-    "mdx_grid_sample_border_fwd": C.c_int, "mdx_grid_sample_border_bwd": C.c_int,
-    "mdx_reprojection_loss_fwd": C.c_int, "mdx_reprojection_loss_bwd": C.c_int, "mdx_ssim_fwd": C.c_int, "mdx_ssim_bwd": C.c_int,
-    "mdx_min_automask_fwd": C.c_int,
-    "mdx_loss_total_fwd": C.c_int, "mdx_loss_total_bwd": C.c_int,
-    "mdx_adam_max_tensors": C.c_int, "mdx_adam_chunk": C.c_int, "mdx_adam_table_entry_bytes": C.c_size_t, "mdx_adam_step": C.c_int,
-    "mdx_pose_projection_fwd": C.c_int, "mdx_pose_projection_bwd": C.c_int,
-    "mdx_bias_act_nhwc_workspace_bytes": C.c_size_t, "mdx_bias_act_nhwc_fwd": C.c_int, "mdx_bias_act_nhwc_bwd": C.c_int,
-    "mdx_mean_bias_nhwc_fwd": C.c_int, "mdx_mean_bias_nhwc_bwd": C.c_int, "mdx_encoder_input_nhwc": C.c_int,
-    "mdx_thin_conv3x3_wgrad_workspace_bytes": C.c_size_t, "mdx_thin_conv3x3_wgrad": C.c_int,
-    "mdx_disp_head_nhwc_workspace_bytes": C.c_size_t, "mdx_disp_head_nhwc_fwd": C.c_int, "mdx_disp_head_nhwc_bwd": C.c_int,
-    "mdx_event_create": C.c_void_p, "mdx_event_destroy": None, "mdx_event_elapsed_us": C.c_int,
-    "mdx_photometric_fwd_timed": C.c_int, "mdx_photometric_bwd_timed": C.c_int,
-    "mdx_decoder_glue_fwd": C.c_int, "mdx_decoder_glue_bwd": C.c_int, "mdx_decoder_glue_workspace_bytes": C.c_size_t,
-    "mdx_maxpool3s2_fwd": C.c_int, "mdx_maxpool3s2_bwd": C.c_int,
-    "mdx_bn_workspace_bytes": C.c_size_t, "mdx_bn_act_fwd": C.c_int, "mdx_bn_act_bwd": C.c_int,
-    "mdx_bn_nhwc_workspace_bytes": C.c_size_t, "mdx_bn_act_nhwc_fwd": C.c_int, "mdx_bn_act_nhwc_bwd": C.c_int,
-    "mdx_decoder_glue_nhwc_fwd": C.c_int, "mdx_decoder_glue_nhwc_bwd": C.c_int,
-    "mdx_decoder_glue_nhwc_workspace_bytes": C.c_size_t, "mdx_maxpool3s2_nhwc_fwd": C.c_int, "mdx_maxpool3s2_nhwc_bwd": C.c_int,
-    "mdx_param2matrix_fwd": C.c_int, "mdx_param2matrix_bwd": C.c_int,
-    "mdx_train_desc_init": C.c_int, "mdx_photometric_train_workspace_bytes": C.c_size_t,
-    "mdx_photometric_train": C.c_int, "mdx_photometric_prologue": C.c_int, "mdx_photometric_train_pre": C.c_int,
-    "mdx_smooth_multi_workspace_bytes": C.c_size_t, "mdx_smooth_loss_multi": C.c_int,
-    "mdx_depth_monitor_workspace_bytes": C.c_size_t, "mdx_depth_monitor": C.c_int,
-    "mdx_resample_ksize": C.c_int, "mdx_resample_plan": C.c_int, "mdx_resample_plan_cols": C.c_int,
-    "mdx_resample_lanczos_u8": C.c_int,
-    "mdx_color_jitter_u8": C.c_int, "mdx_color_convert_u8": C.c_int, "mdx_to_tensor_u8": C.c_int,
-}
+class _Api(object):
+    """api.mdx_x(...): the entry points of include/mdx.h, checked.  A call with more or fewer arguments than the prototype
+    raises TypeError before anything runs (ctypes itself only refuses too few); an int-returning entry point that returns
+    a negative status raises MdxError; anything else returns the result."""
+
+    def __getattr__(self, name):
+        fn = getattr(lib(), name) if name.startswith("mdx_") else None
+        if fn is None or fn.argtypes is None:
+            raise AttributeError("include/mdx.h declares no %s" % name)
+        nargs, status = len(fn.argtypes), fn.restype is C.c_int
+
+        def call(*args):
+            if len(args) != nargs:
+                raise TypeError("%s takes %d arguments (include/mdx.h), %d given" % (name, nargs, len(args)))
+            r = fn(*args)
+            if status and r < 0:
+                check(r, name)
+            return r
+        call.__name__ = name
+        setattr(self, name, call)
+        return call
+
+
+api = _Api()
 
 
 def lib():
-    """Loads libmdx_hip.so; raises MdxError loudly if it is absent or incomplete."""
+    """The typed raw handle of libmdx_hip.so; raises MdxError loudly if it is absent, incomplete or not built from this
+    include/mdx.h."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH) and not os.environ.get("MDX_LIB"):
@@ -100,11 +120,15 @@ def lib():
                            "`python __graft_entry__.py build` (hipcc --offload-arch=gfx950); "
                            "there is no CPU/eager fallback" % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, res in SYMBOLS.items():
+        for name, (res, args) in signatures().items():
             try:
-                getattr(handle, name).restype = res
+                fn = getattr(handle, name)
             except AttributeError:
                 raise MdxError("libmdx_hip.so does not export %s (stale build?)" % name)
+            fn.restype, fn.argtypes = res, args
+        if handle.mdx_version() != DEFINES["VERSION"]:
+            raise MdxError("libmdx_hip.so is MDX_VERSION %d but include/mdx.h says %d (stale build?)"
+                           % (handle.mdx_version(), DEFINES["VERSION"]))
         _lib = handle
     return _lib
 
@@ -145,8 +169,7 @@ def stream():
 
 def make_desc(B, H, W, h, w, S, automask, min_depth, max_depth):
     d = Desc()
-    check(lib().mdx_desc_init(C.byref(d), B, H, W, h, w, S, int(bool(automask)), C.c_double(min_depth),
-                              C.c_double(max_depth)), "mdx_desc_init")
+    api.mdx_desc_init(C.byref(d), B, H, W, h, w, S, int(bool(automask)), min_depth, max_depth)
     return d
 
 
@@ -157,9 +180,8 @@ def make_train_desc(B, H, W, S, hw, automask, min_depth, max_depth, rows_per_chu
     d = TrainDesc()
     hs = (C.c_int32 * len(hw))(*[int(x[0]) for x in hw])
     ws = (C.c_int32 * len(hw))(*[int(x[1]) for x in hw])
-    check(lib().mdx_train_desc_init(C.byref(d), B, H, W, S, len(hw), hs, ws, int(bool(automask)),
-                                    C.c_double(min_depth), C.c_double(max_depth), int(rows_per_chunk)),
-          "mdx_train_desc_init")
+    api.mdx_train_desc_init(C.byref(d), B, H, W, S, len(hw), hs, ws, int(bool(automask)), min_depth, max_depth,
+                            int(rows_per_chunk))
     return d
 
 

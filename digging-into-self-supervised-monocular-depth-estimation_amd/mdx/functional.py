@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr, stream
+from ._lib import api, ptr, stream
 
 
 def _f32c(t):
@@ -33,7 +33,7 @@ class _ComposeProjection(torch.autograd.Function):
         K, T = _f32c(K), _f32c(T)
         B = K.shape[0]
         P = torch.empty(B, 3, 4, device=K.device, dtype=torch.float32)
-        check(lib().mdx_compose_projection(ptr(K), ptr(T), B, ptr(P), stream()), "mdx_compose_projection")
+        api.mdx_compose_projection(ptr(K), ptr(T), B, ptr(P), stream())
         ctx.save_for_backward(K, T)
         return P
 
@@ -63,7 +63,7 @@ def identity_loss(target, sources, desc=None):
     d = desc or _lib.make_desc(B, H, W, H, W, S, True, 0.1, 100.0)
     src = _lib.make_sources(sources)
     out = torch.empty(B, S, H, W, device=target.device, dtype=torch.float32)
-    check(lib().mdx_identity_loss(C.byref(d), ptr(target), C.byref(src), ptr(out), stream()), "mdx_identity_loss")
+    api.mdx_identity_loss(C.byref(d), ptr(target), C.byref(src), ptr(out), stream())
     return out
 
 
@@ -76,7 +76,7 @@ TIMING = None
 def _timing_hook(kind):
     if TIMING is None:
         return None
-    t = _lib.Timing(lib().mdx_event_create(), lib().mdx_event_create())
+    t = _lib.Timing(api.mdx_event_create(), api.mdx_event_create())
     TIMING.setdefault(kind, []).append(t)
     return t
 
@@ -88,10 +88,10 @@ def timing_summary(timing):
         us = []
         for t in pairs:
             v = C.c_float()
-            check(lib().mdx_event_elapsed_us(C.c_void_p(t.start), C.c_void_p(t.stop), C.byref(v)), "mdx_event_elapsed_us")
+            api.mdx_event_elapsed_us(t.start, t.stop, C.byref(v))
             us.append(v.value)
-            lib().mdx_event_destroy(C.c_void_p(t.start))
-            lib().mdx_event_destroy(C.c_void_p(t.stop))
+            api.mdx_event_destroy(t.start)
+            api.mdx_event_destroy(t.stop)
         out[kind] = (sum(us) / max(len(us), 1), len(us))
     return out
 
@@ -129,15 +129,15 @@ class _PhotometricScale(torch.autograd.Function):
             if (cfg.get("need_warp") or keep_warp) else None
         reproj = torch.empty(B, S, H, W, device=dev, dtype=torch.float32) if cfg.get("need_reproj") else None
         coef = torch.empty(B, 9, H, W, device=dev, dtype=torch.float32) if keep_coef else None
-        nws = lib().mdx_photometric_workspace_bytes(C.byref(d))
+        nws = api.mdx_photometric_workspace_bytes(C.byref(d))
         ws = _ws(nws, dev)
         hook = _timing_hook("fwd") if keep_coef else None
-        check(lib().mdx_photometric_fwd_timed(
+        api.mdx_photometric_fwd_timed(
             C.byref(d), ptr(disp), ptr(target), C.byref(src), ptr(invK), ptr(P),
             ptr(ident, optional=True) if automask else None, ptr(noise, optional=True) if automask else None,
             ptr(idx, torch.uint8), ptr(loss_sum), ptr(to_opt, optional=True), ptr(depth, optional=True),
             ptr(warp, optional=True), ptr(reproj, optional=True), ptr(coef, optional=True), ptr(ws, torch.float64),
-            C.c_size_t(nws), stream(), C.byref(hook) if hook is not None else None), "mdx_photometric_fwd")
+            nws, stream(), C.byref(hook) if hook is not None else None)
         ctx.save_for_backward(disp, P, target, invK, idx, *sources)
         ctx.warp = warp if keep_warp else None
         ctx.coef = coef
@@ -158,14 +158,13 @@ class _PhotometricScale(torch.autograd.Function):
         gdisp = torch.empty_like(disp)
         gP = torch.empty(S, B, 3, 4, device=dev, dtype=torch.float32)
         g_dev = _f32c(g_sum.reshape(1))
-        nws = lib().mdx_photometric_workspace_bytes(C.byref(d))
+        nws = api.mdx_photometric_workspace_bytes(C.byref(d))
         ws = _ws(nws, dev)
         hook = _timing_hook("bwd") if ctx.coef is not None else None
-        check(lib().mdx_photometric_bwd_timed(
+        api.mdx_photometric_bwd_timed(
             C.byref(d), ptr(disp), ptr(target), C.byref(src), ptr(invK), ptr(P), ptr(idx, torch.uint8),
-            ptr(ctx.warp, optional=True), ptr(ctx.coef, optional=True), C.c_float(1.0), ptr(g_dev), ptr(gdisp), ptr(gP),
-            ptr(ws, torch.float64),
-            C.c_size_t(nws), stream(), C.byref(hook) if hook is not None else None), "mdx_photometric_bwd")
+            ptr(ctx.warp, optional=True), ptr(ctx.coef, optional=True), 1.0, ptr(g_dev), ptr(gdisp), ptr(gP),
+            ptr(ws, torch.float64), nws, stream(), C.byref(hook) if hook is not None else None)
         return (gdisp, gP, None, None, None, None, None) + (None,) * S
 
 
@@ -197,7 +196,7 @@ class noise_state(object):
         self.tensor = torch.tensor([seed % (1 << 63), 0], dtype=torch.int64, device=device)
 
     def ptr(self):
-        return C.c_void_p(self.tensor.data_ptr())
+        return self.tensor.data_ptr()
 
 
 def photometric_prologue(target, sources, nscales, noises=None, rng=None, automask=True, need_ident=False, advance=False):
@@ -217,12 +216,11 @@ def photometric_prologue(target, sources, nscales, noises=None, rng=None, automa
         raise _lib.MdxError("photometric_prologue: either injected noises or a noise_state")
     if noises is not None:
         noises = [_f32c(x) for x in noises]
-    check(lib().mdx_photometric_prologue(
+    api.mdx_photometric_prologue(
         C.byref(d), ptr(target), C.byref(_lib.make_sources(sources)) if automask else None,
         _lib.ptr_array(noises) if (automask and noises is not None) else None,
         rng.ptr() if (rng is not None and noises is None) else None, int(bool(advance)),
-        ptr(ident, optional=True), ptr(tstat), _lib.ptr_array(bidfi) if automask else None, stream()),
-        "mdx_photometric_prologue")
+        ptr(ident, optional=True), ptr(tstat), _lib.ptr_array(bidfi) if automask else None, stream())
     return dict(tstat=tstat, bidfi=bidfi, ident=ident, rng=(rng if noises is None else None))
 
 
@@ -254,23 +252,22 @@ def _train_launch(cfg, target, invK, ident, noises, sources, Pl, disps):
     depth0 = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if cfg.get("need_depth") else None
     to_opt = [torch.empty(B, H, W, device=dev, dtype=torch.float32) for _ in range(nsc)] \
         if cfg.get("need_to_opt") else None
-    nws = lib().mdx_photometric_train_workspace_bytes(C.byref(d))
+    nws = api.mdx_photometric_train_workspace_bytes(C.byref(d))
     ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
     hook = _timing_hook("train" if grads else "eval")
     tail = (_lib.ptr_array(idx, torch.uint8), ptr(sums), _lib.ptr_array(gdisp) if grads else None,
             ptr(gP) if grads else None, ptr(depth0, optional=True),
-            _lib.ptr_array(to_opt) if to_opt is not None else None, ptr(ws, torch.float64), C.c_size_t(nws), stream(),
+            _lib.ptr_array(to_opt) if to_opt is not None else None, ptr(ws, torch.float64), nws, stream(),
             C.byref(hook) if hook is not None else None)
     if pre is not None:
-        check(lib().mdx_photometric_train_pre(
+        api.mdx_photometric_train_pre(
             C.byref(d), _lib.ptr_array(disps), ptr(target), C.byref(src), ptr(invK), _lib.ptr_array(Ps),
             ptr(pre["tstat"]), _lib.ptr_array(pre["bidfi"]) if automask else None,
-            pre["rng"].ptr() if pre.get("rng") is not None else None, *tail), "mdx_photometric_train_pre")
+            pre["rng"].ptr() if pre.get("rng") is not None else None, *tail)
     else:
-        check(lib().mdx_photometric_train(
+        api.mdx_photometric_train(
             C.byref(d), _lib.ptr_array(disps), ptr(target), C.byref(src), ptr(invK), _lib.ptr_array(Ps),
-            ptr(ident) if automask else None, _lib.ptr_array(noises) if automask else None, *tail),
-            "mdx_photometric_train")
+            ptr(ident) if automask else None, _lib.ptr_array(noises) if automask else None, *tail)
     return dict(sums=sums, idx=idx, gdisp=gdisp, gP=gP, depth0=depth0, to_opt=to_opt, per_scale_P=per_scale_P, pixels=B * H * W)
 
 
@@ -335,10 +332,10 @@ class _SmoothLoss(torch.autograd.Function):
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
         g = torch.empty_like(disp) if need else None
-        nws = lib().mdx_smooth_workspace_bytes(B, h, w)
+        nws = api.mdx_smooth_workspace_bytes(B, h, w)
         ws = _ws(nws, dev)
-        check(lib().mdx_smooth_loss(B, h, w, ptr(disp), ptr(color), int(normalize), ptr(loss), ptr(g, optional=True),
-                                    ptr(ws, torch.float64), C.c_size_t(nws), stream()), "mdx_smooth_loss")
+        api.mdx_smooth_loss(B, h, w, ptr(disp), ptr(color), int(normalize), ptr(loss), ptr(g, optional=True),
+                            ptr(ws, torch.float64), nws, stream())
         if need:
             ctx.save_for_backward(g)
         return loss.reshape(())
@@ -366,11 +363,10 @@ def _smooth_multi_launch(normalize, colors, disps, need):
     ws_ = (C.c_int32 * n)(*[int(d.shape[3]) for d in disps])
     loss = torch.empty(n, device=dev, dtype=torch.float32)
     gs = [torch.empty_like(d) for d in disps] if need else None
-    nws = lib().mdx_smooth_multi_workspace_bytes(n, B, hs, ws_)
+    nws = api.mdx_smooth_multi_workspace_bytes(n, B, hs, ws_)
     ws = _ws(nws, dev)
-    check(lib().mdx_smooth_loss_multi(n, B, hs, ws_, _lib.ptr_array(disps), _lib.ptr_array(colors), int(normalize),
-                                      ptr(loss), _lib.ptr_array(gs) if need else None, ptr(ws, torch.float64),
-                                      C.c_size_t(nws), stream()), "mdx_smooth_loss_multi")
+    api.mdx_smooth_loss_multi(n, B, hs, ws_, _lib.ptr_array(disps), _lib.ptr_array(colors), int(normalize),
+                              ptr(loss), _lib.ptr_array(gs) if need else None, ptr(ws, torch.float64), nws, stream())
     return loss, gs
 
 
@@ -416,8 +412,8 @@ class _TrainLoss(torch.autograd.Function):
         r = _train_launch(cfg, target, invK, ident, noises, sources, Pl, disps)
         total = torch.empty((), device=target.device, dtype=torch.float32)
         scales = (C.c_int32 * nsc)(*[int(v) for v in cfg["scales"]])
-        check(lib().mdx_loss_total_fwd(nsc, ptr(r["sums"]), ptr(smooth), scales, C.c_int64(r["pixels"]),
-                                       C.c_double(cfg["disp_smoothness"]), ptr(total), stream()), "mdx_loss_total_fwd")
+        api.mdx_loss_total_fwd(nsc, ptr(r["sums"]), ptr(smooth), scales, r["pixels"], cfg["disp_smoothness"], ptr(total),
+                               stream())
         if grads:
             ctx.save_for_backward(r["gP"], *r["gdisp"], *gs)
         ctx.meta = (nsc, r["per_scale_P"], [int(v) for v in cfg["scales"]], r["pixels"], float(cfg["disp_smoothness"]),
@@ -438,9 +434,9 @@ class _TrainLoss(torch.autograd.Function):
         gP_out = (torch.empty_like(gP) if per_scale_P else torch.empty_like(gP[0])) if need_P else None
         scales = (C.c_int32 * nsc)(*scale_ids)
         counts = (C.c_int64 * nsc)(*[x.numel() for x in gd])
-        check(lib().mdx_loss_total_bwd(nsc, ptr(g), scales, C.c_int64(pixels), C.c_double(lam), _lib.ptr_array(gd),
-                                       _lib.ptr_array(gs), counts, _lib.ptr_array(out), ptr(gP) if need_P else None, nP,
-                                       int(per_scale_P), ptr(gP_out, optional=True), stream()), "mdx_loss_total_bwd")
+        api.mdx_loss_total_bwd(nsc, ptr(g), scales, pixels, lam, _lib.ptr_array(gd), _lib.ptr_array(gs), counts,
+                               _lib.ptr_array(out), ptr(gP) if need_P else None, nP, int(per_scale_P),
+                               ptr(gP_out, optional=True), stream())
         if gP_out is None:
             gPs = (None,) * len(pdt)
         elif per_scale_P:
@@ -488,8 +484,7 @@ class _Interpolate(torch.autograd.Function):
         x = _f32c(x)
         B, Cc, h, w = x.shape
         out = torch.empty(B, Cc, H, W, device=x.device, dtype=torch.float32)
-        check(lib().mdx_interpolate_bilinear_fwd(ptr(x), B * Cc, h, w, ptr(out), H, W, stream()),
-              "mdx_interpolate_bilinear_fwd")
+        api.mdx_interpolate_bilinear_fwd(ptr(x), B * Cc, h, w, ptr(out), H, W, stream())
         ctx.shape = (B, Cc, h, w, H, W)
         return out
 
@@ -498,8 +493,7 @@ class _Interpolate(torch.autograd.Function):
         B, Cc, h, w, H, W = ctx.shape
         g = _f32c(g)
         gin = torch.empty(B, Cc, h, w, device=g.device, dtype=torch.float32)
-        check(lib().mdx_interpolate_bilinear_bwd(ptr(g), B * Cc, H, W, ptr(gin), h, w, stream()),
-              "mdx_interpolate_bilinear_bwd")
+        api.mdx_interpolate_bilinear_bwd(ptr(g), B * Cc, H, W, ptr(gin), h, w, stream())
         return gin, None, None
 
 
@@ -512,9 +506,7 @@ class _Disp2Depth(torch.autograd.Function):
     def forward(ctx, disp, min_depth, max_depth):
         disp = _f32c(disp)
         sd, depth = torch.empty_like(disp), torch.empty_like(disp)
-        check(lib().mdx_disparity2depth_fwd(ptr(disp), C.c_size_t(disp.numel()), C.c_double(min_depth),
-                                            C.c_double(max_depth), ptr(sd), ptr(depth), stream()),
-              "mdx_disparity2depth_fwd")
+        api.mdx_disparity2depth_fwd(ptr(disp), disp.numel(), min_depth, max_depth, ptr(sd), ptr(depth), stream())
         ctx.save_for_backward(disp)
         ctx.mm = (min_depth, max_depth)
         return sd, depth
@@ -527,9 +519,8 @@ class _Disp2Depth(torch.autograd.Function):
         if gsd is None and gdepth is None:
             return None, None, None
         g = torch.empty_like(disp)
-        check(lib().mdx_disparity2depth_bwd(ptr(disp), ptr(gsd, optional=True), ptr(gdepth, optional=True),
-                                            C.c_size_t(disp.numel()), C.c_double(ctx.mm[0]),
-                                            C.c_double(ctx.mm[1]), ptr(g), stream()), "mdx_disparity2depth_bwd")
+        api.mdx_disparity2depth_bwd(ptr(disp), ptr(gsd, optional=True), ptr(gdepth, optional=True), disp.numel(),
+                                    ctx.mm[0], ctx.mm[1], ptr(g), stream())
         return g, None, None
 
 
@@ -543,7 +534,7 @@ class _Backproject(torch.autograd.Function):
         depth, invK = _f32c(depth), _f32c(invK)
         B, _, H, W = depth.shape
         cam = torch.empty(B, 4, H * W, device=depth.device, dtype=torch.float32)
-        check(lib().mdx_backproject_fwd(ptr(depth), ptr(invK), B, H, W, ptr(cam), stream()), "mdx_backproject_fwd")
+        api.mdx_backproject_fwd(ptr(depth), ptr(invK), B, H, W, ptr(cam), stream())
         ctx.save_for_backward(invK)
         ctx.shape = (B, H, W)
         return cam
@@ -554,7 +545,7 @@ class _Backproject(torch.autograd.Function):
         B, H, W = ctx.shape
         gcam = _f32c(gcam)
         gdepth = torch.empty(B, 1, H, W, device=gcam.device, dtype=torch.float32)
-        check(lib().mdx_backproject_bwd(ptr(gcam), ptr(invK), B, H, W, ptr(gdepth), stream()), "mdx_backproject_bwd")
+        api.mdx_backproject_bwd(ptr(gcam), ptr(invK), B, H, W, ptr(gdepth), stream())
         return gdepth, None
 
 
@@ -568,7 +559,7 @@ class _Project(torch.autograd.Function):
         cam, P = _f32c(cam), _f32c(P)
         B = cam.shape[0]
         grid = torch.empty(B, H, W, 2, device=cam.device, dtype=torch.float32)
-        check(lib().mdx_project_fwd(ptr(cam), ptr(P), B, H, W, C.c_float(eps), ptr(grid), stream()), "mdx_project_fwd")
+        api.mdx_project_fwd(ptr(cam), ptr(P), B, H, W, eps, ptr(grid), stream())
         ctx.save_for_backward(cam, P)
         ctx.dims = (B, H, W, eps)
         return grid
@@ -580,10 +571,10 @@ class _Project(torch.autograd.Function):
         ggrid = _f32c(ggrid)
         gcam = torch.empty_like(cam)
         gP = torch.empty_like(P)
-        nws = lib().mdx_project_workspace_bytes(B, H, W)
+        nws = api.mdx_project_workspace_bytes(B, H, W)
         ws = _ws(nws, cam.device)
-        check(lib().mdx_project_bwd(ptr(cam), ptr(P), ptr(ggrid), B, H, W, C.c_float(eps), ptr(gcam), ptr(gP),
-                                    ptr(ws, torch.float64), C.c_size_t(nws), stream()), "mdx_project_bwd")
+        api.mdx_project_bwd(ptr(cam), ptr(P), ptr(ggrid), B, H, W, eps, ptr(gcam), ptr(gP),
+                            ptr(ws, torch.float64), nws, stream())
         return gcam, gP, None, None, None
 
 
@@ -598,8 +589,7 @@ class _GridSampleBorder(torch.autograd.Function):
         B, Cc, Hi, Wi = img.shape
         _, Ho, Wo, _ = grid.shape
         out = torch.empty(B, Cc, Ho, Wo, device=img.device, dtype=torch.float32)
-        check(lib().mdx_grid_sample_border_fwd(ptr(img), ptr(grid), B, Cc, Hi, Wi, Ho, Wo, ptr(out), stream()),
-              "mdx_grid_sample_border_fwd")
+        api.mdx_grid_sample_border_fwd(ptr(img), ptr(grid), B, Cc, Hi, Wi, Ho, Wo, ptr(out), stream())
         ctx.save_for_backward(img, grid)
         return out
 
@@ -611,8 +601,8 @@ class _GridSampleBorder(torch.autograd.Function):
         gout = _f32c(gout)
         ggrid = torch.empty_like(grid)
         gimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
-        check(lib().mdx_grid_sample_border_bwd(ptr(img), ptr(grid), ptr(gout), B, Cc, Hi, Wi, Ho, Wo, ptr(ggrid),
-                                               ptr(gimg, optional=True), stream()), "mdx_grid_sample_border_bwd")
+        api.mdx_grid_sample_border_bwd(ptr(img), ptr(grid), ptr(gout), B, Cc, Hi, Wi, Ho, Wo, ptr(ggrid),
+                                       ptr(gimg, optional=True), stream())
         return gimg, ggrid
 
 
@@ -626,8 +616,7 @@ class _ReprojectionLoss(torch.autograd.Function):
         pred, target = _f32c(pred), _f32c(target)
         B, _, H, W = pred.shape
         out = torch.empty(B, 1, H, W, device=pred.device, dtype=torch.float32)
-        check(lib().mdx_reprojection_loss_fwd(ptr(pred), ptr(target), B, H, W, ptr(out), stream()),
-              "mdx_reprojection_loss_fwd")
+        api.mdx_reprojection_loss_fwd(ptr(pred), ptr(target), B, H, W, ptr(out), stream())
         ctx.save_for_backward(pred, target)
         return out
 
@@ -640,8 +629,8 @@ class _ReprojectionLoss(torch.autograd.Function):
         gt = torch.empty_like(pred) if ctx.needs_input_grad[1] else None
         if gp is None and gt is None:
             return None, None
-        check(lib().mdx_reprojection_loss_bwd(ptr(pred), ptr(target), ptr(gout), B, H, W, ptr(gp, optional=True),
-                                              ptr(gt, optional=True), stream()), "mdx_reprojection_loss_bwd")
+        api.mdx_reprojection_loss_bwd(ptr(pred), ptr(target), ptr(gout), B, H, W, ptr(gp, optional=True),
+                                      ptr(gt, optional=True), stream())
         return gp, gt
 
 
@@ -655,7 +644,7 @@ class _Ssim(torch.autograd.Function):
         x, y = _f32c(x), _f32c(y)
         B, Cc, H, W = x.shape
         out = torch.empty_like(x)
-        check(lib().mdx_ssim_fwd(ptr(x), ptr(y), B * Cc, H, W, ptr(out), stream()), "mdx_ssim_fwd")
+        api.mdx_ssim_fwd(ptr(x), ptr(y), B * Cc, H, W, ptr(out), stream())
         ctx.save_for_backward(x, y)
         return out
 
@@ -668,8 +657,8 @@ class _Ssim(torch.autograd.Function):
         gy = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         if gx is None and gy is None:
             return None, None
-        check(lib().mdx_ssim_bwd(ptr(x), ptr(y), ptr(gout), B * Cc, H, W, ptr(gx, optional=True), ptr(gy, optional=True),
-                                 stream()), "mdx_ssim_bwd")
+        api.mdx_ssim_bwd(ptr(x), ptr(y), ptr(gout), B * Cc, H, W, ptr(gx, optional=True), ptr(gy, optional=True),
+                         stream())
         return gx, gy
 
 
@@ -689,10 +678,9 @@ def min_automask(ident, noise, reproj, automask=True, need_combined=False):
     comb = torch.empty(B, Cc, H, W, device=dev, dtype=torch.float32) if need_combined else None
     to_opt = torch.empty(B, H, W, device=dev, dtype=torch.float32)
     idx = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
-    check(lib().mdx_min_automask_fwd(ptr(ident, optional=True) if automask else None,
-                                     ptr(noise, optional=True) if automask else None, ptr(reproj), B, S, H, W,
-                                     int(automask), ptr(comb, optional=True), ptr(to_opt), ptr(idx, torch.uint8),
-                                     stream()), "mdx_min_automask_fwd")
+    api.mdx_min_automask_fwd(ptr(ident, optional=True) if automask else None,
+                             ptr(noise, optional=True) if automask else None, ptr(reproj), B, S, H, W,
+                             int(automask), ptr(comb, optional=True), ptr(to_opt), ptr(idx, torch.uint8), stream())
     return to_opt, idx, comb
 
 
@@ -745,10 +733,10 @@ class _DecoderGlue(torch.autograd.Function):
                 raise _lib.MdxError("decoder_glue: bias %s for %d channels" % (tuple(bias.shape), C1))
         out = torch.empty(B, C1 + C2, u * h + 2, u * w + 2, device=raw.device, dtype=out_dtype,
                           memory_format=_CL if cl else torch.contiguous_format)
-        fn = lib().mdx_decoder_glue_nhwc_fwd if cl else lib().mdx_decoder_glue_fwd
-        check(fn(ptr(raw, raw.dtype, cl=cl), ptr(skip, raw.dtype, cl=cl) if skip is not None else None,
-                 ptr(bias) if bias is not None else None, ptr(out, out_dtype, cl=cl), B, C1, C2, h, w,
-                 int(upsample), int(elu), in_code, _DTYPE_CODE[out_dtype], stream()), "mdx_decoder_glue_fwd")
+        fn = api.mdx_decoder_glue_nhwc_fwd if cl else api.mdx_decoder_glue_fwd
+        fn(ptr(raw, raw.dtype, cl=cl), ptr(skip, raw.dtype, cl=cl) if skip is not None else None,
+           ptr(bias) if bias is not None else None, ptr(out, out_dtype, cl=cl), B, C1, C2, h, w,
+           int(upsample), int(elu), in_code, _DTYPE_CODE[out_dtype], stream())
         ctx.save_for_backward(raw, bias)
         ctx.meta = (C2, bool(elu), bool(upsample), out_dtype, cl)
         return out
@@ -768,15 +756,14 @@ class _DecoderGlue(torch.autograd.Function):
         code = _DTYPE_CODE[raw.dtype]
         if bias is not None:
             dbias = torch.empty(C1, device=raw.device, dtype=torch.float32)
-            nws = (lib().mdx_decoder_glue_nhwc_workspace_bytes(B, C1, h, w, code) if cl
-                   else lib().mdx_decoder_glue_workspace_bytes(B, C1, h, w))
+            nws = (api.mdx_decoder_glue_nhwc_workspace_bytes(B, C1, h, w, code) if cl
+                   else api.mdx_decoder_glue_workspace_bytes(B, C1, h, w))
             ws = torch.empty(nws // 4 + 1, device=raw.device, dtype=torch.float32)
-        fn = lib().mdx_decoder_glue_nhwc_bwd if cl else lib().mdx_decoder_glue_bwd
-        check(fn(ptr(gout, out_dtype, cl=cl), ptr(raw, raw.dtype, cl=cl), ptr(bias) if bias is not None else None,
-                 ptr(graw, raw.dtype, cl=cl), ptr(gskip, raw.dtype, cl=cl) if C2 else None,
-                 ptr(dbias) if bias is not None else None, B, C1, C2, h, w, int(upsample), int(elu), code,
-                 _DTYPE_CODE[out_dtype], ptr(ws) if ws is not None else None, C.c_size_t(nws), stream()),
-              "mdx_decoder_glue_bwd")
+        fn = api.mdx_decoder_glue_nhwc_bwd if cl else api.mdx_decoder_glue_bwd
+        fn(ptr(gout, out_dtype, cl=cl), ptr(raw, raw.dtype, cl=cl), ptr(bias) if bias is not None else None,
+           ptr(graw, raw.dtype, cl=cl), ptr(gskip, raw.dtype, cl=cl) if C2 else None,
+           ptr(dbias) if bias is not None else None, B, C1, C2, h, w, int(upsample), int(elu), code,
+           _DTYPE_CODE[out_dtype], ptr(ws) if ws is not None else None, nws, stream())
         return graw, gskip, dbias, None, None, None
 
 
@@ -802,8 +789,8 @@ class _BiasAct(torch.autograd.Function):
         x = _as(x, True)
         b32 = bias if bias.dtype == torch.float32 else bias.float()
         y = torch.empty_like(x)
-        check(lib().mdx_bias_act_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32), ptr(y, x.dtype, cl=True), B, Cc, H, W, int(relu), code,
-                                          stream()), "mdx_bias_act_nhwc_fwd")
+        api.mdx_bias_act_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32), ptr(y, x.dtype, cl=True), B, Cc, H, W, int(relu), code,
+                                  stream())
         ctx.save_for_backward(y)
         ctx.meta = (bool(relu), bias.dtype)
         return y
@@ -817,10 +804,10 @@ class _BiasAct(torch.autograd.Function):
         dy = _as(dy.to(y.dtype), True)
         dx = torch.empty_like(y)
         db = torch.empty(Cc, device=y.device, dtype=torch.float32)
-        nws = lib().mdx_bias_act_nhwc_workspace_bytes(B, Cc, H, W, code)
+        nws = api.mdx_bias_act_nhwc_workspace_bytes(B, Cc, H, W, code)
         ws = torch.empty(nws // 4 + 1, device=y.device, dtype=torch.float32)
-        check(lib().mdx_bias_act_nhwc_bwd(ptr(dy, y.dtype, cl=True), ptr(y, y.dtype, cl=True), ptr(dx, y.dtype, cl=True), ptr(db), B, Cc,
-                                          H, W, int(relu), code, ptr(ws), C.c_size_t(nws), stream()), "mdx_bias_act_nhwc_bwd")
+        api.mdx_bias_act_nhwc_bwd(ptr(dy, y.dtype, cl=True), ptr(y, y.dtype, cl=True), ptr(dx, y.dtype, cl=True), ptr(db), B, Cc,
+                                  H, W, int(relu), code, ptr(ws), nws, stream())
         return dx, db.to(bdt), None
 
 
@@ -846,8 +833,8 @@ class _MeanBias(torch.autograd.Function):
         x = _as(x, True)
         b32 = None if bias is None else (bias if bias.dtype == torch.float32 else bias.float())
         out = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
-        check(lib().mdx_mean_bias_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32) if b32 is not None else None, ptr(out), B, Cc, H, W,
-                                           C.c_float(scale), code, stream()), "mdx_mean_bias_nhwc_fwd")
+        api.mdx_mean_bias_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32) if b32 is not None else None, ptr(out), B, Cc, H, W,
+                                   scale, code, stream())
         ctx.meta = (tuple(x.shape), x.dtype, float(scale), None if bias is None else bias.dtype)
         return out
 
@@ -857,8 +844,8 @@ class _MeanBias(torch.autograd.Function):
         g = _f32c(g)
         dx = torch.empty((B, Cc, H, W), device=g.device, dtype=dt, memory_format=_CL)
         db = torch.empty(Cc, device=g.device, dtype=torch.float32) if bdt is not None else None
-        check(lib().mdx_mean_bias_nhwc_bwd(ptr(g), ptr(dx, dt, cl=True), ptr(db) if db is not None else None, B, Cc, H, W,
-                                           C.c_float(scale), _DTYPE_CODE[dt], stream()), "mdx_mean_bias_nhwc_bwd")
+        api.mdx_mean_bias_nhwc_bwd(ptr(g), ptr(dx, dt, cl=True), ptr(db) if db is not None else None, B, Cc, H, W,
+                                   scale, _DTYPE_CODE[dt], stream())
         return dx, (db.to(bdt) if db is not None else None), None
 
 
@@ -900,8 +887,8 @@ def encoder_input(stack, mean=0.45, std=0.225, dtype=torch.float32):
     blocks, groups = len(stack.blocks), len(stack.blocks[0])
     out = torch.empty((blocks * n, 3 * groups, H, W), device=fr[0].device, dtype=dtype, memory_format=_CL)
     inv = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(std, dtype=torch.float32))
-    check(lib().mdx_encoder_input_nhwc(_lib.ptr_array(fr), blocks, groups, n, H, W, C.c_float(mean), C.c_float(inv),
-                                       ptr(out, dtype, cl=True), _DTYPE_CODE[dtype], stream()), "mdx_encoder_input_nhwc")
+    api.mdx_encoder_input_nhwc(_lib.ptr_array(fr), blocks, groups, n, H, W, mean, inv, ptr(out, dtype, cl=True),
+                               _DTYPE_CODE[dtype], stream())
     return out
 
 
@@ -925,11 +912,10 @@ class _ThinConv3x3(torch.autograd.Function):
             B, Cin, Hp, Wp = x.shape
             gy = _as(gy, True)
             gw = torch.empty_like(weight)
-            nws = lib().mdx_thin_conv3x3_wgrad_workspace_bytes(B, Cin, 16, Hp - 2, Wp - 2)
+            nws = api.mdx_thin_conv3x3_wgrad_workspace_bytes(B, Cin, 16, Hp - 2, Wp - 2)
             ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
-            check(lib().mdx_thin_conv3x3_wgrad(ptr(x, cl=True), ptr(gy, cl=True), ptr(gw, cl="any"), C.c_int64(gw.stride(0)),
-                                               C.c_int64(gw.stride(1)), C.c_int64(gw.stride(2)), C.c_int64(gw.stride(3)), B, Cin, 16,
-                                               Hp - 2, Wp - 2, ptr(ws), C.c_size_t(nws), stream()), "mdx_thin_conv3x3_wgrad")
+            api.mdx_thin_conv3x3_wgrad(ptr(x, cl=True), ptr(gy, cl=True), ptr(gw, cl="any"), gw.stride(0), gw.stride(1),
+                                       gw.stride(2), gw.stride(3), B, Cin, 16, Hp - 2, Wp - 2, ptr(ws), nws, stream())
         return gx, gw
 
 
@@ -962,9 +948,9 @@ class _DispHead(torch.autograd.Function):
             w32 = w32.contiguous()
         b32 = None if bias is None else (bias if bias.dtype == torch.float32 else bias.float())
         disp = torch.empty(B, 1, Hp - 2, Wp - 2, device=x.device, dtype=torch.float32)
-        st = (C.c_int64(w32.stride(1)), C.c_int64(w32.stride(2)), C.c_int64(w32.stride(3)))
-        check(lib().mdx_disp_head_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), *st, ptr(b32) if b32 is not None else None,
-                                           ptr(disp), B, Cc, Hp - 2, Wp - 2, code, stream()), "mdx_disp_head_nhwc_fwd")
+        _, sc, sy, sx = w32.stride()
+        api.mdx_disp_head_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), sc, sy, sx, ptr(b32) if b32 is not None else None,
+                                   ptr(disp), B, Cc, Hp - 2, Wp - 2, code, stream())
         ctx.save_for_backward(x, w32, disp)
         ctx.meta = (weight.dtype, None if bias is None else bias.dtype)
         return disp
@@ -979,12 +965,12 @@ class _DispHead(torch.autograd.Function):
         gx = torch.empty_like(x)
         gw = torch.empty_like(w32)                     # the weight's own strides
         gb = torch.empty(1, device=x.device, dtype=torch.float32) if bdt is not None else None
-        nws = lib().mdx_disp_head_nhwc_workspace_bytes(B, Cc, Hp - 2, Wp - 2, code)
+        nws = api.mdx_disp_head_nhwc_workspace_bytes(B, Cc, Hp - 2, Wp - 2, code)
         ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
-        st = (C.c_int64(w32.stride(1)), C.c_int64(w32.stride(2)), C.c_int64(w32.stride(3)))
-        check(lib().mdx_disp_head_nhwc_bwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), *st, ptr(g), ptr(disp),
-                                           ptr(gx, x.dtype, cl=True), ptr(gw, cl="any"), ptr(gb) if gb is not None else None, B, Cc,
-                                           Hp - 2, Wp - 2, code, ptr(ws), C.c_size_t(nws), stream()), "mdx_disp_head_nhwc_bwd")
+        _, sc, sy, sx = w32.stride()
+        api.mdx_disp_head_nhwc_bwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), sc, sy, sx, ptr(g), ptr(disp),
+                                   ptr(gx, x.dtype, cl=True), ptr(gw, cl="any"), ptr(gb) if gb is not None else None, B, Cc,
+                                   Hp - 2, Wp - 2, code, ptr(ws), nws, stream())
         return gx, gw.to(wdt), (gb.to(bdt) if gb is not None else None)
 
 
@@ -1021,12 +1007,11 @@ class _MaxPool3s2(torch.autograd.Function):
         out = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=x.dtype, memory_format=fmt)
         arg = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=torch.uint8, memory_format=fmt)
         if cl:
-            check(lib().mdx_maxpool3s2_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(out, x.dtype, cl=True),
-                                                ptr(arg, torch.uint8, cl=True), B, Cc, H, W, code, stream()),
-                  "mdx_maxpool3s2_nhwc_fwd")
+            api.mdx_maxpool3s2_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(out, x.dtype, cl=True),
+                                        ptr(arg, torch.uint8, cl=True), B, Cc, H, W, code, stream())
         else:
-            check(lib().mdx_maxpool3s2_fwd(ptr(x, x.dtype), ptr(out, x.dtype), ptr(arg, torch.uint8), B * Cc, H, W, code,
-                                           stream()), "mdx_maxpool3s2_fwd")
+            api.mdx_maxpool3s2_fwd(ptr(x, x.dtype), ptr(out, x.dtype), ptr(arg, torch.uint8), B * Cc, H, W, code,
+                                   stream())
         ctx.save_for_backward(arg)
         ctx.meta = (H, W, x.dtype, cl)
         ctx.set_materialize_grads(False)
@@ -1042,12 +1027,12 @@ class _MaxPool3s2(torch.autograd.Function):
             return None, None
         gin = torch.empty(B, Cc, H, W, device=gout.device, dtype=dtype, memory_format=_CL if cl else torch.contiguous_format)
         if cl:
-            check(lib().mdx_maxpool3s2_nhwc_bwd(ptr(gout, dtype, cl=True), ptr(gout2, dtype, cl=True) if gout2 is not None else None,
-                                                ptr(arg, torch.uint8, cl=True), ptr(gin, dtype, cl=True), B, Cc, H, W,
-                                                _DTYPE_CODE[dtype], stream()), "mdx_maxpool3s2_nhwc_bwd")
+            api.mdx_maxpool3s2_nhwc_bwd(ptr(gout, dtype, cl=True), ptr(gout2, dtype, cl=True) if gout2 is not None else None,
+                                        ptr(arg, torch.uint8, cl=True), ptr(gin, dtype, cl=True), B, Cc, H, W,
+                                        _DTYPE_CODE[dtype], stream())
         else:
-            check(lib().mdx_maxpool3s2_bwd(ptr(gout, dtype), ptr(arg, torch.uint8), ptr(gin, dtype), B * Cc, H, W,
-                                           _DTYPE_CODE[dtype], stream()), "mdx_maxpool3s2_bwd")
+            api.mdx_maxpool3s2_bwd(ptr(gout, dtype), ptr(arg, torch.uint8), ptr(gin, dtype), B * Cc, H, W,
+                                   _DTYPE_CODE[dtype], stream())
         return gin, None
 
 
@@ -1093,14 +1078,13 @@ class _BnAct(torch.autograd.Function):
         save_mean = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
         save_invstd = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
         Bg = B // groups
-        nws = lib().mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code) if cl else lib().mdx_bn_workspace_bytes(Bg, Cc, H, W)
+        nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code) if cl else api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
         ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
-        fn = lib().mdx_bn_act_nhwc_fwd if cl else lib().mdx_bn_act_fwd
-        check(fn(ptr(x, x.dtype, cl=cl), ptr(res, x.dtype, cl=cl) if res is not None else None, ptr(weight), ptr(bias),
-                 ptr(running_mean) if running_mean is not None else None,
-                 ptr(running_var) if running_var is not None else None, ptr(y, x.dtype, cl=cl), ptr(save_mean),
-                 ptr(save_invstd), Bg, Cc, H, W, groups, C.c_float(eps), C.c_float(momentum), int(relu), code, ptr(ws),
-                 C.c_size_t(nws), stream()), "mdx_bn_act_fwd")
+        fn = api.mdx_bn_act_nhwc_fwd if cl else api.mdx_bn_act_fwd
+        fn(ptr(x, x.dtype, cl=cl), ptr(res, x.dtype, cl=cl) if res is not None else None, ptr(weight), ptr(bias),
+           ptr(running_mean) if running_mean is not None else None,
+           ptr(running_var) if running_var is not None else None, ptr(y, x.dtype, cl=cl), ptr(save_mean),
+           ptr(save_invstd), Bg, Cc, H, W, groups, eps, momentum, int(relu), code, ptr(ws), nws, stream())
         # channels-last float32, ReLU, no residual: backward re-derives the ReLU mask from x (y is not read: one map less per pass;
         # 760.3 -> 765.4 images/s.  bfloat16 maps: 1498 -> 1492 -- the re-derivation costs more than half a map of traffic)
         mask_from_x = cl and bool(relu) and res is None and x.dtype == torch.float32
@@ -1129,21 +1113,21 @@ class _BnAct(torch.autograd.Function):
         dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(Cc, device=x.device, dtype=torch.float32)
         if cl:
-            nws = lib().mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code)
+            nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code)
             ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
-            check(lib().mdx_bn_act_nhwc_bwd(
+            api.mdx_bn_act_nhwc_bwd(
                 ptr(dy, x.dtype, cl=True), ptr(dy2, x.dtype, cl=True) if dy2 is not None else None,
                 ptr(y, x.dtype, cl=True) if y is not None else None, ptr(x, x.dtype, cl=True), ptr(weight),
                 ptr(bias) if bias is not None else None, ptr(save_mean), ptr(save_invstd), ptr(dx, x.dtype, cl=True),
                 ptr(dres, x.dtype, cl=True) if has_res else None, ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups, int(relu),
-                code, ptr(ws), C.c_size_t(nws), stream()), "mdx_bn_act_nhwc_bwd")
+                code, ptr(ws), nws, stream())
         else:
-            nws = lib().mdx_bn_workspace_bytes(Bg, Cc, H, W)
+            nws = api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
             ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
-            check(lib().mdx_bn_act_bwd(
+            api.mdx_bn_act_bwd(
                 ptr(dy, x.dtype), ptr(y, x.dtype), ptr(x, x.dtype), ptr(weight), ptr(save_mean), ptr(save_invstd),
                 ptr(dx, x.dtype), ptr(dres, x.dtype) if has_res else None, ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups,
-                int(relu), code, ptr(ws), C.c_size_t(nws), stream()), "mdx_bn_act_bwd")
+                int(relu), code, ptr(ws), nws, stream())
         return (dx, dres, dgamma, dbeta) + (None,) * 7
 
 
@@ -1169,7 +1153,7 @@ class _Param2Matrix(torch.autograd.Function):
         if tr.shape[0] != N:
             raise _lib.MdxError("param2matrix: %d rotations, %d translations" % (N, tr.shape[0]))
         M = torch.empty(N, 4, 4, device=aa.device, dtype=torch.float32)
-        check(lib().mdx_param2matrix_fwd(ptr(aa), ptr(tr), N, int(invert), ptr(M), stream()), "mdx_param2matrix_fwd")
+        api.mdx_param2matrix_fwd(ptr(aa), ptr(tr), N, int(invert), ptr(M), stream())
         ctx.save_for_backward(aa, tr)
         ctx.meta = (bool(invert), axisangle.shape, translation.shape)
         return M
@@ -1180,8 +1164,8 @@ class _Param2Matrix(torch.autograd.Function):
         invert, sa, st = ctx.meta
         gM = _f32c(gM)
         gaa, gtr = torch.empty_like(aa), torch.empty_like(tr)
-        check(lib().mdx_param2matrix_bwd(ptr(aa), ptr(tr), ptr(gM), aa.shape[0], int(invert), ptr(gaa), ptr(gtr),
-                                         stream()), "mdx_param2matrix_bwd")
+        api.mdx_param2matrix_bwd(ptr(aa), ptr(tr), ptr(gM), aa.shape[0], int(invert), ptr(gaa), ptr(gtr),
+                                 stream())
         return gaa.reshape(sa), gtr.reshape(st), None
 
 
@@ -1200,8 +1184,7 @@ class _PoseProjection(torch.autograd.Function):
         T = torch.empty(S, B, 4, 4, device=raw.device, dtype=torch.float32)
         P = torch.empty(S, B, 3, 4, device=raw.device, dtype=torch.float32)
         sel = tuple((C.c_int32 * S)(*[int(v) for v in a]) for a in (row0, frame, invert))
-        check(lib().mdx_pose_projection_fwd(ptr(raw), M, F, ptr(K), B, S, *sel, ptr(T), ptr(P), stream()),
-              "mdx_pose_projection_fwd")
+        api.mdx_pose_projection_fwd(ptr(raw), M, F, ptr(K), B, S, *sel, ptr(T), ptr(P), stream())
         ctx.save_for_backward(raw, K)
         ctx.meta = (B, [int(v) for v in row0], [int(v) for v in frame], [int(v) for v in invert])
         return T, P
@@ -1214,10 +1197,9 @@ class _PoseProjection(torch.autograd.Function):
         S = len(row0)
         graw = torch.empty_like(raw)
         sel = tuple((C.c_int32 * S)(*a) for a in (row0, frame, invert))
-        check(lib().mdx_pose_projection_bwd(ptr(raw), M, F, ptr(K), B, S, *sel,
-                                            ptr(_f32c(gP)) if gP is not None else None,
-                                            ptr(_f32c(gT)) if gT is not None else None, ptr(graw), stream()),
-              "mdx_pose_projection_bwd")
+        api.mdx_pose_projection_bwd(ptr(raw), M, F, ptr(K), B, S, *sel,
+                                    ptr(_f32c(gP)) if gP is not None else None,
+                                    ptr(_f32c(gT)) if gT is not None else None, ptr(graw), stream())
         return graw, None, None, None, None, None
 
 
@@ -1242,9 +1224,8 @@ def depth_monitor(pred, gt, window, min_depth=1e-3, max_depth=80.0):
     _, _, gh, gw = gt.shape
     r0, r1, c0, c1 = (int(v) for v in window)
     out = torch.empty(8, device=pred.device, dtype=torch.float32)
-    nws = lib().mdx_depth_monitor_workspace_bytes(B, r0, r1, c0, c1)
+    nws = api.mdx_depth_monitor_workspace_bytes(B, r0, r1, c0, c1)
     ws = _ws(nws, pred.device)
-    check(lib().mdx_depth_monitor(ptr(pred), B, h, w, ptr(gt), gh, gw, r0, r1, c0, c1, C.c_float(min_depth),
-                                  C.c_float(max_depth), ptr(out), ptr(ws, torch.float64), C.c_size_t(nws), stream()),
-          "mdx_depth_monitor")
+    api.mdx_depth_monitor(ptr(pred), B, h, w, ptr(gt), gh, gw, r0, r1, c0, c1, min_depth, max_depth, ptr(out),
+                          ptr(ws, torch.float64), nws, stream())
     return out

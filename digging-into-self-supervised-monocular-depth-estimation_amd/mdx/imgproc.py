@@ -60,14 +60,12 @@ class plan_cache(object):
         key = (int(in_size), int(out_size))
         plan = self.plans.get(key)
         if plan is None:
-            lib = _lib.lib()
-            ksize = lib.mdx_resample_ksize(key[0], key[1])
-            if ksize <= 0:
-                _lib.check(ksize, "mdx_resample_ksize")
+            ksize = _lib.api.mdx_resample_ksize(key[0], key[1])
+            if ksize == 0:
+                raise _lib.MdxError("mdx_resample_ksize(%d, %d) returned no taps" % key)
             bounds = np.zeros((key[1], 2), np.int32)
             kk = np.zeros((ksize, key[1]), np.int32)          # tap-major (include/mdx.h)
-            _lib.check(lib.mdx_resample_plan(key[0], key[1], bounds.ctypes.data_as(C.c_void_p),
-                                             kk.ctypes.data_as(C.c_void_p)), "mdx_resample_plan")
+            _lib.api.mdx_resample_plan(key[0], key[1], bounds.ctypes.data, kk.ctypes.data)
             tb, tk = torch.from_numpy(bounds).to(self.device), torch.from_numpy(kk).to(self.device)
             # (device addresses kept beside the tensors: a batch asks for ~150 plans, data_ptr() is not free)
             plan = self.plans[key] = Plan(ksize, tb, tk, tb.data_ptr(), tk.data_ptr(), None, 0, 0, 0)
@@ -76,12 +74,10 @@ class plan_cache(object):
         if cols and self.cols and plan.cols is None:
             # the same weights column-major, zero-padded, both directions: what the rows form of the horizontal pass reads
             # with scalar loads (include/mdx.h, mdx_resample_plan_cols)
-            lib = _lib.lib()
             lead, row = C.c_int(0), C.c_int(0)
-            _lib.check(lib.mdx_resample_plan_cols(key[0], key[1], C.byref(lead), C.byref(row), None), "mdx_resample_plan_cols")
+            _lib.api.mdx_resample_plan_cols(key[0], key[1], C.byref(lead), C.byref(row), None)
             kc = np.zeros((2, key[1], row.value), np.int32)
-            _lib.check(lib.mdx_resample_plan_cols(key[0], key[1], C.byref(lead), C.byref(row),
-                                                  kc.ctypes.data_as(C.c_void_p)), "mdx_resample_plan_cols")
+            _lib.api.mdx_resample_plan_cols(key[0], key[1], C.byref(lead), C.byref(row), kc.ctypes.data)
             tc = torch.from_numpy(kc).to(self.device)
             plan = self.plans[key] = plan._replace(cols=tc, cols_ptr=tc.data_ptr(), cols_lead=lead.value, cols_row=row.value)
             torch.cuda.current_stream(self.device).synchronize()
@@ -154,8 +150,7 @@ def resize_lanczos_multi(plans, sources, sizes, flips, outs):
     jobs["xkc"], jobs["xkc_lead"], jobs["xkc_row"] = xa[:, :, 3], xa[:, :, 4], xa[:, :, 5]
     jobs["ybounds"], jobs["ykk"], jobs["yksize"] = ya[:, :, 0], ya[:, :, 1], ya[:, :, 2]
     jobs = jobs.reshape(-1)
-    _lib.check(_lib.lib().mdx_resample_lanczos_u8(jobs.ctypes.data_as(C.c_void_p), len(jobs), _lib.stream()),
-               "mdx_resample_lanczos_u8")
+    _lib.api.mdx_resample_lanczos_u8(jobs.ctypes.data, len(jobs), _lib.stream())
     inter.record_stream(torch.cuda.current_stream(dev))
     return results
 
@@ -191,8 +186,7 @@ def color_jitter(src_u8, params, out=None):
     jobs["hue_shift"] = [int(q[4]) for q in sel]
     if not out.is_contiguous() or out.shape != (N, 3, h, w) or out.dtype != torch.float32:
         raise _lib.MdxError("color_jitter: out must be a contiguous float32 [N,3,h,w] tensor")
-    _lib.check(_lib.lib().mdx_color_jitter_u8(jobs.ctypes.data_as(C.c_void_p), len(todo), _lib.stream()),
-               "mdx_color_jitter_u8")
+    _lib.api.mdx_color_jitter_u8(jobs.ctypes.data, len(todo), _lib.stream())
     lsum.record_stream(torch.cuda.current_stream(dev))
     return out
 
@@ -203,8 +197,7 @@ def color_convert(src_u8, mode):
     code = {"hsv": 0, "rgb": 1, "L": 2}[mode]
     n = src_u8.shape[1]
     dst = torch.empty((n,) if code == 2 else (3, n), dtype=torch.uint8, device=src_u8.device)
-    _lib.check(_lib.lib().mdx_color_convert_u8(code, C.c_void_p(src_u8.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                               C.c_size_t(n), _lib.stream()), "mdx_color_convert_u8")
+    _lib.api.mdx_color_convert_u8(code, src_u8.data_ptr(), dst.data_ptr(), n, _lib.stream())
     return dst
 
 
@@ -217,8 +210,7 @@ def to_tensor(src_u8):
     src = src_u8.contiguous()
     dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
     if src.numel():
-        _lib.check(_lib.lib().mdx_to_tensor_u8(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                               C.c_size_t(src.numel()), _lib.stream()), "mdx_to_tensor_u8")
+        _lib.api.mdx_to_tensor_u8(src.data_ptr(), dst.data_ptr(), src.numel(), _lib.stream())
     return dst
 
 

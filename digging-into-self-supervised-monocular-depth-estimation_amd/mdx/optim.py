@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import check, lib, stream
+from ._lib import api, stream
 
 
 class _Table(C.Structure):
@@ -28,7 +28,7 @@ class Adam(torch.optim.Adam):
         plan = self._plans.get(gi)
         if plan is not None and plan["key"] == key:
             return plan
-        assert C.sizeof(_Table) == lib().mdx_adam_table_entry_bytes()
+        assert C.sizeof(_Table) == api.mdx_adam_table_entry_bytes()
         dev = params[0].device
         n = len(params)
         host = (_Table * n)()
@@ -36,7 +36,7 @@ class Adam(torch.optim.Adam):
             host[i] = _Table(p.data_ptr(), m.data_ptr(), v.data_ptr(), s.data_ptr(), p.numel())
         raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone()
         table = raw.to(dev)
-        chunk, per = lib().mdx_adam_chunk(), lib().mdx_adam_max_tensors()
+        chunk, per = api.mdx_adam_chunk(), api.mdx_adam_max_tensors()
         launches = []
         for first in range(0, n, per):
             count = min(per, n - first)
@@ -87,14 +87,12 @@ class Adam(torch.optim.Adam):
             plan = self._plan(gi, params, exp_avgs, exp_avg_sqs, steps)
             torch._foreach_add_(steps, 1)
             lr = group["lr"]
-            lr_ptr = C.c_void_p(lr.data_ptr()) if torch.is_tensor(lr) else None
+            lr_ptr = lr.data_ptr() if torch.is_tensor(lr) else None
             if torch.is_tensor(lr) and not (lr.is_cuda and lr.dtype == torch.float32):
                 lr, lr_ptr = float(lr), None
             beta1, beta2 = group["betas"]
             for first, count, blockmap, nblocks in plan["launches"]:
                 garr = (C.c_void_p * count)(*[g.data_ptr() for g in grads[first:first + count]])
-                check(lib().mdx_adam_step(C.c_void_p(plan["table"].data_ptr()), first, count, garr,
-                                          C.c_void_p(blockmap.data_ptr()), nblocks, lr_ptr,
-                                          C.c_double(0.0 if lr_ptr is not None else float(lr)), C.c_double(beta1), C.c_double(beta2),
-                                          C.c_double(group["eps"]), stream()), "mdx_adam_step")
+                api.mdx_adam_step(plan["table"].data_ptr(), first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr,
+                                  0.0 if lr_ptr is not None else float(lr), beta1, beta2, group["eps"], stream())
         return None

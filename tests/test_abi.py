@@ -1,14 +1,19 @@
-"""CPU: the C-ABI library loads and exports every symbol include/mdx.h declares; host-side argument
-validation (no kernel is launched, no GPU needed)."""
+"""CPU: the C-ABI library loads and exports every symbol include/mdx.h declares, typed and laid out as the header says;
+host-side argument validation (no kernel is launched, no GPU needed)."""
+import ast
 import ctypes as C
+import glob
 import importlib
 import os
 import re
+import subprocess
 
+import numpy as np
 import pytest
 
-importlib.import_module("digging-into-self-supervised-monocular-depth-estimation_amd")
-from mdx import _lib  # noqa: E402
+PKG = "digging-into-self-supervised-monocular-depth-estimation_amd"
+importlib.import_module(PKG)
+from mdx import _lib, imgproc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,10 +24,102 @@ def header_functions():
     return sorted(set(re.findall(r"\b(mdx_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_header_and_binding_agree():
+def test_header_signatures_bound_to_library():
+    """Every entry point the header declares has a parsed prototype of known types (signatures() raises on any other) and
+    the library exports it, typed as parsed."""
     names = header_functions()
+    sigs = _lib.signatures()
     assert len(names) >= 25
-    assert set(names) == set(_lib.SYMBOLS), set(names) ^ set(_lib.SYMBOLS)
+    assert set(names) == set(sigs), set(names) ^ set(sigs)
+    lib = _lib.lib()
+    for name, (res, args) in sigs.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+@pytest.mark.parametrize("name, restype, argtypes", [
+    ("mdx_photometric_fwd", C.c_int, [C.c_void_p] * 16 + [C.c_size_t, C.c_void_p]),
+    ("mdx_photometric_train_pre", C.c_int, [C.c_void_p] * 16 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("mdx_ssim_bwd", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    ("mdx_loss_total_fwd", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    ("mdx_mean_bias_nhwc_fwd", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
+    ("mdx_version", C.c_int, []),
+    ("mdx_status_string", C.c_char_p, [C.c_int]),
+    ("mdx_smooth_workspace_bytes", C.c_size_t, [C.c_int] * 3),
+    ("mdx_event_create", C.c_void_p, []),
+    ("mdx_event_destroy", None, [C.c_void_p]),
+])
+def test_prototypes_parsed_from_the_header(name, restype, argtypes):
+    assert _lib.signatures()[name] == (restype, argtypes)
+
+
+def test_call_sites_pass_the_prototypes_argument_count():
+    """Every call of an attribute named like an entry point (api.mdx_x(...), lib().mdx_x(...)) without *args, in the package,
+    tools/ and tests/, passes exactly the prototype's number of arguments: GPU-only code is checked here, on the CPU."""
+    sigs = _lib.signatures()
+    files = (glob.glob(os.path.join(ROOT, PKG, "**", "*.py"), recursive=True) + glob.glob(os.path.join(ROOT, "tools", "*.py"))
+             + glob.glob(os.path.join(ROOT, "tests", "*.py")))
+    calls, bad = 0, []
+    for f in files:
+        with open(f) as fh:
+            tree = ast.parse(fh.read(), f)
+        for node in ast.walk(tree):
+            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in sigs
+                    and not any(isinstance(a, ast.Starred) for a in node.args)):
+                calls += 1
+                if len(node.args) + len(node.keywords) != len(sigs[node.func.attr][1]):
+                    bad.append("%s:%d %s" % (os.path.relpath(f, ROOT), node.lineno, node.func.attr))
+    assert calls >= 100 and not bad, (calls, bad)
+
+
+def test_api_checks_argument_count_type_and_status():
+    """api: the argument count is checked before anything runs (ctypes alone passes extra arguments on), the argument types
+    by ctypes, a negative status raises MdxError naming the entry point and the status; other results are returned."""
+    args = (None, None, None, 3, 8, 8, None, None, None)
+    for wrong in (args[:-1], args + (None,)):
+        with pytest.raises(TypeError, match="mdx_ssim_bwd takes 9 arguments"):
+            _lib.api.mdx_ssim_bwd(*wrong)
+    with pytest.raises(_lib.MdxError, match=r"mdx_ssim_bwd failed: MDX_ERR_NULL_POINTER \(-2\)"):
+        _lib.api.mdx_ssim_bwd(*args)
+    with pytest.raises(C.ArgumentError):
+        _lib.api.mdx_ssim_bwd(None, None, None, 3.0, 8, 8, None, None, None)      # a float for an int parameter
+    assert _lib.api.mdx_version() == _lib.DEFINES["VERSION"]
+    assert _lib.api.mdx_smooth_workspace_bytes(1, 32, 64) == _lib.lib().mdx_smooth_workspace_bytes(1, 32, 64) > 0
+    with pytest.raises(AttributeError):
+        _lib.api.mdx_no_such_entry
+
+
+def test_stale_library_is_refused(monkeypatch):
+    """A library whose mdx_version() is not the header's MDX_VERSION would be bound with types it was not built with."""
+    monkeypatch.setitem(_lib.DEFINES, "VERSION", _lib.DEFINES["VERSION"] + 1)
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(_lib.MdxError, match="stale build"):
+        _lib.lib()
+
+
+LAYOUTS = {"mdx_desc": _lib.Desc, "mdx_train_desc": _lib.TrainDesc, "mdx_sources": _lib.Sources, "mdx_timing": _lib.Timing,
+           "mdx_resample_job": imgproc.RESAMPLE_JOB, "mdx_jitter_job": imgproc.JITTER_JOB}
+
+
+def test_struct_layouts_match_the_header(tmp_path):
+    """sizeof, and offsetof / sizeof of every field, of the header's structs as the host C compiler lays them out == the
+    ctypes structures and numpy records the binding fills."""
+    want, code = [], []
+    for name, t in LAYOUTS.items():
+        if isinstance(t, np.dtype):
+            fields, size = [(f, t.fields[f][1], t.fields[f][0].itemsize) for f in t.names], t.itemsize
+        else:
+            fields, size = [(f, getattr(t, f).offset, getattr(t, f).size) for f, _ in t._fields_], C.sizeof(t)
+        want.append("%s %d" % (name, size))
+        code.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        for f, off, sz in fields:
+            want.append("%s.%s %d %d" % (name, f, off, sz))
+            code.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (name, f, name, f, name, f))
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include "mdx.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(code))
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    assert subprocess.check_output([exe], text=True).splitlines() == want
 
 
 def test_library_exports_every_declared_symbol():
@@ -54,14 +151,14 @@ def test_desc_init_rejects_bad_shapes(args):
     assert rc == -1   # MDX_ERR_BAD_SHAPE
 
 
-def test_null_pointers_and_workspace_are_reported_not_crashed():
+def test_null_pointers_and_workspace_report_status_codes():
     lib = _lib.lib()
     d = _lib.make_desc(1, 32, 64, 32, 64, 2, True, 0.1, 100.0)
     assert lib.mdx_photometric_workspace_bytes(C.byref(d)) > 0
     assert lib.mdx_smooth_workspace_bytes(1, 32, 64) > 0
     assert lib.mdx_project_workspace_bytes(1, 32, 64) > 0
     assert lib.mdx_photometric_fwd(C.byref(d), None, None, None, None, None, None, None, None, None, None, None,
-                                   None, None, None, C.c_size_t(0), None) == -2
+                                   None, None, None, None, C.c_size_t(0), None) == -2
     assert lib.mdx_compose_projection(None, None, 1, None, None) == -2
     assert lib.mdx_smooth_loss(1, 32, 64, None, None, 1, None, None, None, C.c_size_t(0), None) == -2
     with pytest.raises(_lib.MdxError):

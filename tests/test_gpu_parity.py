@@ -30,8 +30,8 @@ def _P(G, c):
 
 
 def test_library_loaded(G):
-    from mdx import lib, LIB_PATH
-    assert lib().mdx_version() == 510
+    from mdx import api, LIB_PATH
+    assert api.mdx_version() == 510
     assert LIB_PATH.endswith("libmdx_hip.so")
 
 

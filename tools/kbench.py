@@ -38,7 +38,7 @@ def main():
                     help="0: backward re-warps; 1: forward stores the warp; 2: SSIM coefficient maps only (training form); 3: both")
     a = ap.parse_args()
     dev = "cuda:0"
-    lib = _lib.lib()
+    api = _lib.api
     B, H, W, S = a.B, a.H, a.W, a.S
     g = torch.Generator().manual_seed(0)
     base = torch.rand(B, 3, H // 4, W // 4, generator=g)
@@ -72,34 +72,33 @@ def main():
         coef = torch.empty(B, 9, H, W, device=dev)
         color_s = torch.nn.functional.avg_pool2d(tgt, 2 ** s) if s else tgt
         d = _lib.make_desc(B, H, W, h, w, S, True, 0.1, 100.0)
-        nws = lib.mdx_photometric_workspace_bytes(C.byref(d))
+        nws = api.mdx_photometric_workspace_bytes(C.byref(d))
         ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device=dev)
         gdisp, gP = torch.empty_like(disp), torch.empty(S, B, 3, 4, device=dev)
         loss = torch.empty(1, device=dev)
-        nsw = lib.mdx_smooth_workspace_bytes(B, h, w)
+        nsw = api.mdx_smooth_workspace_bytes(B, h, w)
         sws = torch.empty(nsw // 8 + 1, dtype=torch.float64, device=dev)
 
         def fwd():
-            _lib.check(lib.mdx_photometric_fwd(
+            api.mdx_photometric_fwd(
                 C.byref(d), _lib.ptr(disp), _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), _lib.ptr(P),
                 _lib.ptr(ident), _lib.ptr(noise), _lib.ptr(idx, torch.uint8), None, None, None,
                 _lib.ptr(warp) if a.save_warp in (1, 3) else None, None, _lib.ptr(coef) if a.save_warp >= 2 else None,
-                _lib.ptr(ws, torch.float64), C.c_size_t(nws), _lib.stream()), "fwd")
+                _lib.ptr(ws, torch.float64), nws, _lib.stream())
 
         def bwd():
-            _lib.check(lib.mdx_photometric_bwd(
+            api.mdx_photometric_bwd(
                 C.byref(d), _lib.ptr(disp), _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), _lib.ptr(P),
                 _lib.ptr(idx, torch.uint8), _lib.ptr(warp) if a.save_warp in (1, 3) else None,
-                _lib.ptr(coef) if a.save_warp >= 2 else None, C.c_float(1e-6), None, _lib.ptr(gdisp), _lib.ptr(gP),
-                _lib.ptr(ws, torch.float64), C.c_size_t(nws), _lib.stream()), "bwd")
+                _lib.ptr(coef) if a.save_warp >= 2 else None, 1e-6, None, _lib.ptr(gdisp), _lib.ptr(gP),
+                _lib.ptr(ws, torch.float64), nws, _lib.stream())
 
         def ident_fn():
             F.identity_loss(tgt, srcs)
 
         def smooth():
-            _lib.check(lib.mdx_smooth_loss(B, h, w, _lib.ptr(disp), _lib.ptr(color_s), 1, _lib.ptr(loss),
-                                           _lib.ptr(gdisp), _lib.ptr(sws, torch.float64), C.c_size_t(nsw),
-                                           _lib.stream()), "smooth")
+            api.mdx_smooth_loss(B, h, w, _lib.ptr(disp), _lib.ptr(color_s), 1, _lib.ptr(loss), _lib.ptr(gdisp),
+                                _lib.ptr(sws, torch.float64), nsw, _lib.stream())
         fwd()
         fns = {"fwd": fwd, "bwd": bwd, "ident": ident_fn, "smooth": smooth}
         out = []
@@ -146,27 +145,26 @@ def main():
         sums = torch.empty(nsc, device=dev)
         gdisps = [torch.empty_like(x) for x in disps]
         gPs = torch.empty(nsc, S, B, 3, 4, device=dev)
-        nws = lib.mdx_photometric_train_workspace_bytes(C.byref(td))
+        nws = api.mdx_photometric_train_workspace_bytes(C.byref(td))
         ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
         pd, pP = _lib.ptr_array([x.detach() for x in disps]), _lib.ptr_array([P] * nsc)
         pi, pg, pb = _lib.ptr_array(idxs, torch.uint8), _lib.ptr_array(gdisps), _lib.ptr_array(pre["bidfi"])
 
         def train_pre(grads, hook=None):
-            _lib.check(lib.mdx_photometric_train_pre(
+            api.mdx_photometric_train_pre(
                 C.byref(td), pd, _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), pP, _lib.ptr(pre["tstat"]), pb, None, pi,
                 _lib.ptr(sums), pg if grads else None, _lib.ptr(gPs) if grads else None, None, None,
-                _lib.ptr(ws, torch.float64), C.c_size_t(nws), _lib.stream(), C.byref(hook) if hook is not None else None),
-                "train_pre")
+                _lib.ptr(ws, torch.float64), nws, _lib.stream(), C.byref(hook) if hook is not None else None)
 
         def kernel_us(grads):
-            hooks = [_lib.Timing(lib.mdx_event_create(), lib.mdx_event_create()) for _ in range(a.reps)]
+            hooks = [_lib.Timing(api.mdx_event_create(), api.mdx_event_create()) for _ in range(a.reps)]
             for hk in hooks:
                 train_pre(grads, hk)
             torch.cuda.synchronize()
             us = []
             for hk in hooks:
                 v = C.c_float()
-                _lib.check(lib.mdx_event_elapsed_us(C.c_void_p(hk.start), C.c_void_p(hk.stop), C.byref(v)), "elapsed")
+                api.mdx_event_elapsed_us(hk.start, hk.stop, C.byref(v))
                 us.append(v.value)
             return sum(us) / len(us)
         t_call = timeit(lambda: train_pre(True))
@@ -186,16 +184,16 @@ def main():
         sums = torch.empty(nsc, device=dev)
         gdisps = [torch.empty_like(x) for x in disps]
         gPs = torch.empty(nsc, S, B, 3, 4, device=dev)
-        nws = lib.mdx_photometric_train_workspace_bytes(C.byref(td))
+        nws = api.mdx_photometric_train_workspace_bytes(C.byref(td))
         ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
         pd, pP, pn = _lib.ptr_array(disps), _lib.ptr_array([P] * nsc), _lib.ptr_array(noises)
         pi, pg = _lib.ptr_array(idxs, torch.uint8), _lib.ptr_array(gdisps)
 
         def train(hook=None):
-            _lib.check(lib.mdx_photometric_train(
+            api.mdx_photometric_train(
                 C.byref(td), pd, _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), pP, _lib.ptr(ident), pn, pi,
-                _lib.ptr(sums), pg, _lib.ptr(gPs), None, None, _lib.ptr(ws, torch.float64), C.c_size_t(nws),
-                _lib.stream(), C.byref(hook) if hook is not None else None), "train")
+                _lib.ptr(sums), pg, _lib.ptr(gPs), None, None, _lib.ptr(ws, torch.float64), nws,
+                _lib.stream(), C.byref(hook) if hook is not None else None)
         for _ in range(3):
             train()
         e0, e1 = ev(), ev()
@@ -204,14 +202,14 @@ def main():
             train()
         e1.record()
         e1.synchronize()
-        hooks = [_lib.Timing(lib.mdx_event_create(), lib.mdx_event_create()) for _ in range(a.reps)]
+        hooks = [_lib.Timing(api.mdx_event_create(), api.mdx_event_create()) for _ in range(a.reps)]
         for hk in hooks:
             train(hk)
         torch.cuda.synchronize()
         us = []
         for hk in hooks:
             v = C.c_float()
-            _lib.check(lib.mdx_event_elapsed_us(C.c_void_p(hk.start), C.c_void_p(hk.stop), C.byref(v)), "elapsed")
+            api.mdx_event_elapsed_us(hk.start, hk.stop, C.byref(v))
             us.append(v.value)
         if os.environ.get("MDX_TRAIN_STAMPS"):   # diagnostic library build: per-item phase clocks at the workspace's end
             items = int(os.environ["MDX_TRAIN_STAMPS"])
