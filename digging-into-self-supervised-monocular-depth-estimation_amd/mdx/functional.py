@@ -1144,6 +1144,30 @@ def bn_act(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1, r
                         int(groups), bool(fork))
 
 
+# ---- eval-mode BatchNorm2d fused with residual add and ReLU (csrc/norm_infer.hip) -------------------------------------
+def bn_act_infer(x, weight, bias, running_mean, running_var, eps=1e-5, residual=None, relu=True, fork=False):
+    """Eval-mode batch norm of x [B,C,H,W] with the RUNNING statistics, then `+ residual`, then ReLU, in one launch
+    (csrc/norm_infer.hip; channels-last when x is, else planar -- as bn_act, a channel count the channels-last kernel refuses
+    takes the planar one).  The statistics are read, never written.  float32 or bfloat16 activations, float32 parameters.
+    No autograd node: for callers that need no gradient (torch.no_grad(), or an input that does not require one).
+    fork: the result twice, as bn_act returns it."""
+    code = _glue_dtype(x, "bn_act_infer")
+    B, Cc, H, W = x.shape
+    cl = is_channels_last(x) and _nhwc_ok(x.dtype, Cc)
+    x = _as(x, cl)
+    if residual is not None:
+        if residual.shape != x.shape or residual.dtype != x.dtype:
+            raise _lib.MdxError("bn_act_infer: residual %s %s does not match x %s %s"
+                                % (tuple(residual.shape), residual.dtype, tuple(x.shape), x.dtype))
+        residual = _as(residual, cl)
+    y = torch.empty_like(x)
+    fn = api.mdx_bn_act_nhwc_infer if cl else api.mdx_bn_act_infer
+    fn(ptr(x, x.dtype, cl=cl), ptr(residual, x.dtype, cl=cl) if residual is not None else None, ptr(_f32c(weight)),
+       ptr(_f32c(bias)), ptr(_f32c(running_mean)), ptr(_f32c(running_var)), ptr(y, x.dtype, cl=cl), B, Cc, H, W, float(eps),
+       int(bool(relu)), code, stream())
+    return (y, y.view_as(y)) if fork else y
+
+
 # ---- param2matrix (csrc/pose.hip) ----------------------------------------------------------------------------------
 class _Param2Matrix(torch.autograd.Function):
     @staticmethod

@@ -47,9 +47,12 @@ def _weights(modules):
 @contextlib.contextmanager
 def bf16_weights(modules):
     """While the block runs, `module.weight` of every convolution in `modules` is a bfloat16 copy that autograd links to the
-    float32 parameter; the copies and, in backward, the float32 gradients are one launch each."""
+    float32 parameter; the copies and, in backward, the float32 gradients are one launch each.  With grad disabled (validation)
+    the copies are the same one launch and nothing is linked.  Either way they are made HERE, from the parameters as they are
+    now: a captured step re-makes them at every replay, where a cast cached by autocast before the capture would be replayed
+    stale after the optimiser has moved the weights."""
     sites = _weights(modules)
-    if not sites or not torch.is_grad_enabled():
+    if not sites:
         yield 0
         return
     shadows = _CastAll.apply(*[p for _, _, p in sites])

@@ -23,6 +23,7 @@ class BatchNorm2d(nn.BatchNorm2d):
     which does read the counter) keeps the stock behaviour."""
 
     fused_min_elements = 0          # per channel (B*H*W): below it act() takes the torch ops (a test / A-B switch)
+    fused_eval = True               # False: act() in eval mode takes the torch ops (a test / A-B switch)
     _batch_groups = 1               # default of every instance; batch_groups() sets it on the modules of ONE network
 
     @staticmethod
@@ -69,8 +70,17 @@ class BatchNorm2d(nn.BatchNorm2d):
 
     def act(self, x, residual=None, relu=True, fork=False):
         """relu(self(x) + residual) -- on the GPU in training mode as the fused kernels of csrc/norm.hip (planar maps) /
-        csrc/norm_nhwc.hip (channels-last maps): statistics pass + normalise/add/ReLU pass, backward likewise; else as the
-        torch ops.  fork: the result twice (mdx.functional.bn_act), one tensor per consumer."""
+        csrc/norm_nhwc.hip (channels-last maps): statistics pass + normalise/add/ReLU pass, backward likewise; in eval mode,
+        when no gradient is wanted, as the one-launch kernel of csrc/norm_infer.hip; else as the torch ops.
+        fork: the result twice (mdx.functional.bn_act), one tensor per consumer."""
+        if not self.training and self._eval_fused(x, residual):
+            # csrc/norm_infer.hip: the running statistics folded into one scale and shift per channel, one launch; nothing
+            # is updated in eval mode (neither the statistics nor the host-side batch counter)
+            from mdx import functional as F
+            if residual is not None and residual.dtype != x.dtype:
+                residual = residual.to(x.dtype)
+            return F.bn_act_infer(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
+                                  residual=residual, relu=relu, fork=fork)
         # csrc/norm.hip: one launch each way for maps up to 24 K elements per channel (kept in registers between the
         # reduction and the apply step), two (statistics pass, apply pass) above -- tools/normbench.py
         fused = (self.training and x.is_cuda and self.track_running_stats and self.momentum is not None
@@ -91,6 +101,14 @@ class BatchNorm2d(nn.BatchNorm2d):
             residual = residual.to(x.dtype)
         return F.bn_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
                         residual=residual, relu=relu, groups=self._batch_groups, fork=fork)
+
+    def _eval_fused(self, x, residual):
+        """Eval mode on the GPU with nothing to differentiate: the fused eval kernel serves act()."""
+        if not (self.fused_eval and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 4
+                and self.track_running_stats and self.affine and self.running_mean is not None):
+            return False
+        return not torch.is_grad_enabled() or not any(
+            t is not None and t.requires_grad for t in (x, residual, self.weight, self.bias))
 
     def _flush_counter(self):
         if self._pending_batches and self.num_batches_tracked is not None:

@@ -46,6 +46,8 @@ def options(argv=None):
                    help="DataLoader workers stack only the entries a step reads")
     p.add_argument("--graph", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True,
                    help="single-GPU training: capture the step into one hipGraph and replay it (host launch cost off the critical path)")
+    p.add_argument("--graph_valid", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True,
+                   help="with --graph: capture the validation step (no grad, networks in eval mode) into a hipGraph of its own too")
     p.add_argument("--device_prefetch", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True,
                    help="upload the next batch on a side stream while the current step computes")
     p.add_argument("--gpu_image_prep", type=str, default="auto", choices=["auto", "true", "false"],

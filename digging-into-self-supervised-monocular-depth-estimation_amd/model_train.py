@@ -68,6 +68,21 @@ class device_prefetcher(object):
             yield cur
 
 
+def _plain(v):
+    """A captured step's outputs as plain tensors (detached, containers kept)."""
+    if torch.is_tensor(v):
+        return v.detach()
+    if isinstance(v, (list, tuple)):
+        return type(v)(_plain(x) for x in v)
+    return v
+
+
+def _static_keys(tr):
+    """The batch entries a captured step reads, copied into its static buffers (the velodyne ground truth is read by
+    control.metric from the batch itself, never by the step)."""
+    return lambda k: tr.compute._step_reads(k) and not (isinstance(k, tuple) and k[0] == "depth")
+
+
 class graphed_step(object):
     """One training step (networks, the photometric kernels launched through the C-ABI, the gradient all-reduce of a
     data-parallel job, fused Adam) captured into ONE hipGraph and replayed: ~1600 kernel launches leave the host's
@@ -99,8 +114,7 @@ class graphed_step(object):
         for g in opt.param_groups:
             g["capturable"] = True
             g["lr"] = self.lr
-        # the velodyne ground truth is read by control.metric from the batch itself, never by the captured step
-        wanted = lambda k: tr.compute._step_reads(k) and not (isinstance(k, tuple) and k[0] == "depth")  # noqa: E731
+        wanted = _static_keys(tr)
         self.static = {k: (v.to(dev).clone() if torch.is_tensor(v) and wanted(k) else v) for k, v in example.items()}
         self.copied = {k for k, v in example.items() if torch.is_tensor(v) and wanted(k)}
         from model_layer.depth_encoder import BatchNorm2d
@@ -157,12 +171,6 @@ class graphed_step(object):
                 outputs = tr._eager_step(dict(self.static))
         # the graph's output tensors, without the autograd graph behind them: a loss that kept its grad_fn would keep the
         # capture pass's gradient-accumulation nodes (created on the capture stream) alive into later eager steps
-        def _plain(v):
-            if torch.is_tensor(v):
-                return v.detach()
-            if isinstance(v, (list, tuple)):
-                return type(v)(_plain(x) for x in v)
-            return v
         self.outputs = {k: _plain(v) for k, v in outputs.items()}
         del outputs
         self.bn_incr = [m._pending_batches - b for m, b in zip(self.bns, before)]
@@ -186,10 +194,63 @@ class graphed_step(object):
         return self.outputs
 
 
+class graphed_valid_step(object):
+    """The validation step -- torch.no_grad(), the networks in eval mode (batch norm as csrc/norm_infer.hip with the running
+    statistics), the forward-only form of the loss kernels -- captured into ONE hipGraph of its own and replayed: a few hundred
+    mostly small launches leave the host, as graphed_step does for the training step.  Same contract: the batch is copied into
+    static device buffers, the outputs are the graph's own tensors (detached), control.metric reads them on the main stream.
+    Its own memory pool; no collective inside (the epoch means' all-reduce stays where it is).  The warm-up passes the capture
+    needs draw auto-mask noise, so the generator's offset is put back afterwards: every replay then advances it exactly as one
+    eager validation step does.  Weights are read where they live: the training updates them in place, and under --amp bf16 the
+    weight shadows (mdx/shadow.py) are re-made inside the graph at every replay."""
+
+    def __init__(self, tr, example, warmup=2):
+        self.tr = tr
+        dev = tr.device
+        self.wanted = wanted = _static_keys(tr)
+        self.static = {k: (v.to(dev).clone() if torch.is_tensor(v) and wanted(k) else v) for k, v in example.items()}
+        self.copied = {k for k, v in example.items() if torch.is_tensor(v) and wanted(k)}
+        tr.setting.set_valid()
+        rng = tr.compute.noise_rng(dev) if tr.compute.draws_in_kernel() else None
+        saved_rng = rng.tensor.clone() if rng is not None else None
+        self.stream = torch.cuda.Stream(dev)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad():
+            with torch.cuda.stream(self.stream):
+                for _ in range(warmup):
+                    tr.batch_process(dict(self.static))
+                if rng is not None:
+                    rng.tensor.copy_(saved_rng)
+            torch.cuda.current_stream(dev).wait_stream(self.stream)
+            torch.cuda.synchronize(dev)
+            self.graph = torch.cuda.CUDAGraph()
+            # thread_local: see graphed_step (the loader's pin-memory thread allocates while this thread captures)
+            with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+                outputs = tr.batch_process(dict(self.static))
+        self.outputs = {k: _plain(v) for k, v in outputs.items()}
+        del outputs
+        torch.cuda.synchronize(dev)
+        self.replays = 0
+
+    def matches(self, inputs):
+        """Does the batch fit the static buffers (same entries, same shapes and dtypes)?"""
+        have = {k for k, v in inputs.items() if torch.is_tensor(v) and self.wanted(k)}
+        return have == self.copied and all(inputs[k].shape == self.static[k].shape and inputs[k].dtype == self.static[k].dtype
+                                           for k in self.copied)
+
+    def __call__(self, inputs):
+        for k in self.copied:
+            self.static[k].copy_(inputs[k], non_blocking=True)
+        self.graph.replay()
+        self.replays += 1
+        return self.outputs
+
+
 class trainer(object):
     def __init__(self, opt):
         self.opt = opt
         self._graphed = None
+        self._graphed_valid = None
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if torch.cuda.is_available():
@@ -227,7 +288,8 @@ class trainer(object):
     def batch_process(self, inputs):
         # bf16 networks: every convolution weight cast ONCE, by one launch, before the two networks fork (and the weight gradients
         # back by one launch at the end of backward) instead of by autocast around each convolution (mdx/shadow.py)
-        if (self.compute.amp == "bf16" and str(self.device).startswith("cuda") and torch.is_grad_enabled()
+        # (validation, torch.no_grad(): the same one launch, no autograd node)
+        if (self.compute.amp == "bf16" and str(self.device).startswith("cuda")
                 and getattr(self.opt, "shadow_weights", True)):
             from mdx.shadow import bf16_weights
             with bf16_weights(self.setting.raw_model.values()):
@@ -310,6 +372,23 @@ class trainer(object):
             torch.cuda.current_stream(self.device).wait_stream(mon)
         return self._graphed(inputs)
 
+    def valid_step(self, inputs):
+        """One validation step (the caller holds torch.no_grad() and has put the networks in eval mode).  opt.graph and
+        opt.graph_valid (GPU, capturable): captured once into graphed_valid_step and replayed for every batch of the captured
+        shape; otherwise -- or for a batch of another shape -- eager."""
+        use_graph = (getattr(self.opt, "graph", False) and getattr(self.opt, "graph_valid", True) and self.can_graph())
+        if not use_graph:
+            return self.batch_process(inputs)
+        inputs = self.compute.prepare(inputs)     # decoded frames -> step entries (a no-op after the prefetcher)
+        if self._graphed_valid is None:
+            self._graphed_valid = graphed_valid_step(self, inputs)
+        if not self._graphed_valid.matches(inputs):
+            return self.batch_process(inputs)
+        mon = getattr(self.control, "_side", None)
+        if mon is not None:                       # the depth monitor of the previous step reads the graph's outputs
+            torch.cuda.current_stream(self.device).wait_stream(mon)
+        return self._graphed_valid(inputs)
+
     def train(self):
         names = self.control.metric_name
         epoch_train = {k: [] for k in names}
@@ -332,7 +411,7 @@ class trainer(object):
             self.setting.set_valid()
             for step, valid_inputs in enumerate(self.batches(self.setting.valid_dataloader)):
                 with torch.no_grad():
-                    valid_outputs = self.batch_process(valid_inputs)
+                    valid_outputs = self.valid_step(valid_inputs)
                     batch_valid = self.control.metric(valid_inputs, valid_outputs, batch_valid)
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break

@@ -358,6 +358,21 @@ int mdx_bn_act_bwd(const void *dy, const void *y, const void *x, const float *ga
                    const float *save_invstd, void *dx, void *dres, float *dgamma, float *dbeta, int B, int C, int H,
                    int W, int groups, int relu, int dtype, void *workspace, size_t workspace_bytes, void *stream);
 
+/* EVAL-mode BatchNorm2d + residual add + ReLU (csrc/norm_infer.hip; model_layer/depth_encoder.py BatchNorm2d.act when the
+ * module is not training): y = act(x * s + t [+ res]) per channel, s = gamma / sqrt(run_var + eps), t = beta - run_mean * s,
+ * what torch.nn.functional.batch_norm(training=False) computes.  One launch, no workspace, no atomics; the running
+ * statistics are read, never written.  x, res, y float32 (dtype 0) or bfloat16 (dtype 1); gamma, beta, run_mean, run_var
+ * [C] float32; res may be NULL, every other pointer must not be; relu 0 / 1.
+ * mdx_bn_act_infer: planar [B][C][H][W], any C and H * W, element-aligned pointers.
+ * mdx_bn_act_nhwc_infer: channels-last [B][H][W][C]; C a multiple of 4 (float32) / 8 (bfloat16) and x, res, y 16-byte aligned,
+ * else MDX_ERR_BAD_SHAPE / MDX_ERR_MISALIGNED (the caller then takes the planar entry point). */
+int mdx_bn_act_infer(const void *x, const void *res, const float *gamma, const float *beta, const float *run_mean,
+                     const float *run_var, void *y, int B, int C, int H, int W, float eps, int relu, int dtype,
+                     void *stream);
+int mdx_bn_act_nhwc_infer(const void *x, const void *res, const float *gamma, const float *beta, const float *run_mean,
+                          const float *run_var, void *y, int B, int C, int H, int W, float eps, int relu, int dtype,
+                          void *stream);
+
 /* ---- the same network glue for CHANNELS-LAST maps (memory [B][H][W][C]; csrc/norm_nhwc.hip, csrc/glue_nhwc.hip) ----
  * What MIOpen's implicit-GEMM convolutions read and write without a layout transpose on either side.  Same operators,
  * same arithmetic and summation order per element as the planar entry points above; a thread owns one 16-byte channel

@@ -7,6 +7,8 @@ per pass that has to touch it: forward x [+ res] -> y; backward dy, y, x -> dx [
 the layouts whatever their launch count.
 
     python tools/netbench.py [--bf16] [--config 1|3] [--json out.json]
+    python tools/netbench.py --eval [--bf16] [--json out.json]   # eval-mode batch norm (csrc/norm_infer.hip) against
+                                                                  # torch's batch_norm + add + relu, maps of configs[1] and [3]
 """
 import argparse
 import importlib
@@ -104,14 +106,63 @@ def pool_case(B, C, H, W, dt, cl):
     return tf, tb, x.numel() * es + gy.numel() * (es + 1), gy.numel() * (es + 1) + x.numel() * es
 
 
+def eval_case(B, C, H, W, has_res, dt, cl):
+    """Eval-mode batch norm [+ res] + ReLU: mdx.functional.bn_act_infer (one launch) against the torch ops (batch_norm(training=False),
+    add, relu); algorithmic bytes x [+ res] read, y written."""
+    import torch.nn.functional as TF
+    x = torch.randn(B, C, H, W, device="cuda").to(dt).contiguous(memory_format=fmt(cl))
+    res = torch.randn(B, C, H, W, device="cuda").to(dt).contiguous(memory_format=fmt(cl)) if has_res else None
+    w, b = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda")
+    rm, rv = torch.randn(C, device="cuda"), torch.rand(C, device="cuda") + 0.5
+
+    def fused():
+        return F.bn_act_infer(x, w, b, rm, rv, 1e-5, residual=res, relu=True)
+
+    def ops():
+        y = TF.batch_norm(x, rm, rv, w, b, False, 0.1, 1e-5)
+        return TF.relu(y + res if has_res else y)
+    with torch.no_grad():
+        tf, tt = graph_time(fused), graph_time(ops)
+    return tf, tt, x.numel() * x.element_size() * (2 + (1 if has_res else 0))
+
+
+def main_eval(a, dt):
+    out = []
+    print("%-44s %-6s %28s %28s" % ("bn_act_infer B C HxW res", "layout", "fused us (GB/s, frac 8 TB/s)", "torch ops us (GB/s)"))
+    for config in (1, 3):
+        if config == 1:
+            B, H0, W0, ch = 12, 192, 640, (64, 64, 128, 256, 512)
+        else:
+            B, H0, W0, ch = 8, 320, 1024, (64, 256, 512, 1024, 2048)
+        shapes = [(B, ch[0], H0 // 2, W0 // 2, False)]
+        for i, c in enumerate(ch[1:]):
+            hh, ww = H0 // (4 << i), W0 // (4 << i)
+            shapes += [(B, c, hh, ww, False), (B, c, hh, ww, True)]
+            if config == 3:
+                shapes += [(B, c // 4, hh, ww, False)]
+        for (b, c, hh, ww, res) in shapes:
+            for cl in (False, True):
+                tf, tt, nb = eval_case(b, c, hh, ww, res, dt, cl)
+                name = "configs[%d] B=%d C=%d %dx%d res=%d" % (config, b, c, hh, ww, res)
+                print("%-44s %-6s %9.1f (%5.0f, %.2f)          %9.1f (%5.0f)" % (
+                    name, "nhwc" if cl else "nchw", tf, nb / tf / 1e3, nb / tf / 1e3 / 8000.0, tt, nb / tt / 1e3), flush=True)
+                out.append({"op": "bn_act_infer " + name, "layout": "nhwc" if cl else "nchw", "dtype": str(dt), "fused_us": tf,
+                            "torch_ops_us": tt, "bytes": nb, "fused_frac_hbm": nb / tf / 1e3 / 8000.0})
+    if a.json:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--config", type=int, default=1, choices=[1, 3])
     ap.add_argument("--json", type=str, default="")
     ap.add_argument("--only", type=str, default="", help="bn | glue | pool: only this family")
+    ap.add_argument("--eval", action="store_true", help="eval-mode batch norm against the torch ops, configs[1] and [3]")
     a = ap.parse_args()
     dt = torch.bfloat16 if a.bf16 else torch.float32
+    if a.eval:
+        return main_eval(a, dt)
     if a.config == 1:       # ResNet-18, 192x640, batch 12 (depth) / 2 x 12 (both pose pairs in one batch)
         B, H0, W0, ch = 12, 192, 640, (64, 64, 128, 256, 512)
     else:                   # ResNet-50, 320x1024, batch 8
