@@ -15,6 +15,12 @@
 // histograms in LDS, then one pass of sums; double partial sums added in a fixed order.  Bilinear taps are
 // mdx_device.hpp's (ATen's CPU arithmetic).  Round 2's form histogrammed the window with global atomics (two 16-bit
 // passes, 0.36 M atomics on clustered bins: 97 us of its 155 us) and re-derived every masked pixel three times.
+//
+// A NaN prediction at a masked pixel is carried, not clamped away (fminf / fmaxf would turn it into min_depth and a
+// diverged network would report plausible numbers): it stays NaN in the compact array (one fixed bit pattern, which sorts
+// above every depth), the first radix pass records it in the selection state, and the finishing pass then writes NaN to
+// all seven numbers -- what torch.clamp and torch.median give.  out[7] is still the number of valid pixels.  A NaN under
+// invalid ground truth or outside the window touches nothing.
 #include "mdx_common.hpp"
 #include "mdx_device.hpp"
 
@@ -29,7 +35,8 @@ struct MonArgs {
     int B, h, w, gh, gw, r0, r1, c0, c1;
     float lo, hi;
     unsigned *count;       // [blocks]: masked pixels of each block of the window
-    unsigned *sel;         // [16]: n, -, -, -, -, -, median bits gt, median bits pred | per array: n, prefix, rank, blocks done
+    unsigned *sel;         // [16]: n, a masked prediction was NaN, -, -, -, -, median bits gt, median bits pred |
+                           //       per array: n, prefix, rank, blocks done
     unsigned *ghist;       // [2][2048]: the radix passes' global histograms (zero between passes)
     double *part;          // [MON_MB][7]
     float *cg, *cp;        // [n]: ground truth / clamped upsampled prediction of the masked pixels, in pixel order
@@ -38,7 +45,9 @@ struct MonArgs {
     unsigned nblk;
 };
 
-// the masked pixel of window index i: ground truth and the clamped, upsampled prediction
+constexpr unsigned MON_NAN = 0x7fc00000u;    // the one pattern of a NaN prediction in cp (not the radix passes' padding key)
+
+// the masked pixel of window index i: ground truth and the clamped, upsampled prediction (NaN stays NaN)
 MDX_DEV bool mon_pixel(const MonArgs &a, unsigned i, float &g, float &p)
 {
     const unsigned ww = (unsigned)(a.c1 - a.c0), wh = (unsigned)(a.r1 - a.r0);
@@ -48,7 +57,7 @@ MDX_DEV bool mon_pixel(const MonArgs &a, unsigned i, float &g, float &p)
     g = a.gt[((size_t)b * a.gh + gy) * a.gw + gx];
     if (!(g > 0.f)) return false;
     const float v = upsample_at(a.pred + (size_t)b * a.h * a.w, a.h, a.w, a.gh, a.gw, gy, gx, a.premul != 0);
-    p = fminf(fmaxf(v, a.lo), a.hi);
+    p = v != v ? __uint_as_float(MON_NAN) : fminf(fmaxf(v, a.lo), a.hi);
     return true;
 }
 
@@ -160,12 +169,14 @@ __global__ __launch_bounds__(1024) void mon_radix_kernel(MonArgs a)
     }
     s_hist[threadIdx.x] = 0; s_hist[threadIdx.x + 1024] = 0;
     __syncthreads();
+    bool nan_seen = false;
     for (unsigned i0 = blockIdx.x * 8192u; i0 < n; i0 += MON_RB * 8192u) {
         unsigned key[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const unsigned i = i0 + u * 1024u + threadIdx.x;
             key[u] = i < n ? __float_as_uint(v[i]) : 0xffffffffu;          // (no depth has these bits: clamped to [lo, hi])
+            if (PASS == 0) nan_seen |= which == 1 && key[u] == MON_NAN;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
@@ -173,6 +184,7 @@ __global__ __launch_bounds__(1024) void mon_radix_kernel(MonArgs a)
                 atomicAdd(&s_hist[(key[u] >> SH) & (unsigned)(BINS - 1)], 1u);
     }
     __syncthreads();
+    if (PASS == 0 && nan_seen) atomicOr(&a.sel[1], 1u);                     // mon_finish_kernel reports NaN
     for (int k = threadIdx.x; k < BINS; k += 1024)
         if (s_hist[k]) atomicAdd(&ghist[k], s_hist[k]);
     __threadfence();
@@ -226,7 +238,10 @@ __global__ __launch_bounds__(NT) void mon_metric_kernel(MonArgs a)
         acc[2] += t < 1.953125f ? 1.0 : 0.0;
         const float d = g - p;
         acc[3] += (double)(d * d);
-        const float l = logf(g) - logf(p);
+        // log g - log p.  With p near g the difference of two rounded logarithms keeps no digits (each carries ~1e-7 of
+        // |log g|, and the difference may be as small as that: rmse_log was 2e-3 off for p = g (1 +- 1e-4)); there g - p
+        // is exact (g and p within a factor of two) and log1p keeps them all
+        const float l = fabsf(d) < 0.5f * p ? log1pf(d / p) : logf(g) - logf(p);
         acc[4] += (double)(l * l);
         acc[5] += (double)(fabsf(d) / g);
         acc[6] += (double)((d * d) / g);
@@ -266,8 +281,8 @@ __global__ __launch_bounds__(NT) void mon_finish_kernel(MonArgs a, int nblk)
         }
         const double n = (double)a.sel[0];
         const float nanv = __uint_as_float(0x7fc00000u);
-        if (a.sel[0] == 0) {
-            for (int q = 0; q < 7; ++q) a.out[q] = nanv;       // torch's mean / median of an empty selection
+        if (a.sel[0] == 0 || a.sel[1] != 0) {                  // torch's mean / median of an empty selection, or of one
+            for (int q = 0; q < 7; ++q) a.out[q] = nanv;       // that holds a NaN prediction
         } else {
             a.out[0] = (float)(t[5] / n);          // abs_rel
             a.out[1] = (float)(t[6] / n);          // sq_rel

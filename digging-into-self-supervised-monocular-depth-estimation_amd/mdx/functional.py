@@ -1241,8 +1241,12 @@ def pose_projection(raw, K, row0, frame, invert):
 # ---- train-time depth monitor (csrc/monitor.hip) -------------------------------------------------------------------
 def depth_monitor(pred, gt, window, min_depth=1e-3, max_depth=80.0):
     """compute_depth_metric's seven numbers (reference model_metric.py:70-105) + the number of valid pixels, as a
-    float32 tensor [8] on the device: six small launches, no compaction, no sort, no synchronisation.
-    pred [B,1,h,w], gt [B,1,gh,gw]; window = (r0, r1, c0, c1) of the ground-truth image."""
+    float32 tensor [8] on the device: seven small launches (count, compact the masked pixels, three radix-selection passes
+    for the two exact lower medians, sums, finish), no sort, no synchronisation.
+    pred [B,1,h,w], gt [B,1,gh,gw]; window = (r0, r1, c0, c1) of the ground-truth image.
+    No valid pixel in the window: seven NaNs and out[7] = 0.  A NaN prediction at a valid window pixel (after the
+    bilinear resize): seven NaNs, as torch.clamp and torch.median give, and out[7] = the number of valid pixels; a NaN
+    outside the window or under invalid ground truth changes nothing."""
     pred, gt = _f32c(pred), _f32c(gt)
     B, _, h, w = pred.shape
     _, _, gh, gw = gt.shape

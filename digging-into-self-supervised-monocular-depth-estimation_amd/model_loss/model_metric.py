@@ -70,6 +70,8 @@ def compute_depth_metric(inputs, outputs, lib="torch"):
     buffer (torch.nonzero_static over the crop window; the lidar ground truth covers ~7 % of it, the buffer holds a
     sixth) and every statistic is a masked reduction over that buffer: same numbers, nothing leaves the device.  If
     more pixels are valid than the buffer holds the metrics come out as NaN (visible in the log, never silently wrong).
+    A NaN prediction at a valid pixel of the window makes all seven numbers NaN on the GPU (csrc/monitor.hip), as the
+    reference's torch.clamp and torch.median do; it is never clamped into a depth.
     """
     gt = inputs[("depth", 0)]
     gh, gw = gt.shape[-2:]
@@ -77,7 +79,7 @@ def compute_depth_metric(inputs, outputs, lib="torch"):
     r0, r1 = int(0.40810811 * gh), int(0.99189189 * gh)
     c0, c1 = int(0.03594771 * gw), int(0.96405229 * gw)
     if lib == "torch" and gt.is_cuda and pred.is_cuda and gt.dtype == torch.float32 and pred.dtype == torch.float32:
-        # GPU: the hand-written monitor (csrc/monitor.hip): exact medians by radix selection, six small launches
+        # GPU: the hand-written monitor (csrc/monitor.hip): exact medians by radix selection, seven small launches
         # (the torch-op form below costs ~100 kernels and two sorts: 2.0 ms against ~0.05 ms per step at batch 12)
         from mdx import functional as F
         out = F.depth_monitor(pred, gt, (r0, r1, c0, c1), 1e-3, 80.0)

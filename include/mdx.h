@@ -454,8 +454,10 @@ int mdx_maxpool3s2_nhwc_bwd(const void *gout, const void *gout2, const uint8_t *
 /* Train-time depth monitor   replaces model_loss/model_metric.py:70-105 (called every step, model_train.py:69).
  * pred [B,1,h,w] (outputs[("depth",0,0)]), gt [B,1,gh,gw] (0 = no return); window rows r0:r1, cols c0:c1 (the Garg crop).
  * out [8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, number of valid pixels.  Bilinear resize to the ground truth's
- * size, clamp, batch-level median scaling (torch.median's lower median, exact), clamp, compute_depth_error -- without
- * compacting or sorting: two 16-bit radix-histogram passes find the medians. */
+ * size, clamp, batch-level median scaling (torch.median's lower median, exact), clamp, compute_depth_error -- the masked
+ * pixels are compacted on the device and three radix-selection passes (11 / 11 / 10 bits) find the medians; nothing is
+ * sorted and nothing leaves the device.  A NaN prediction at a valid window pixel makes all seven numbers NaN (as
+ * torch.clamp and torch.median do); out[7] is still the number of valid pixels. */
 size_t mdx_depth_monitor_workspace_bytes(int B, int r0, int r1, int c0, int c1);
 int mdx_depth_monitor(const float *pred, int B, int h, int w, const float *gt, int gh, int gw, int r0, int r1, int c0,
                       int c1, float min_depth, float max_depth, float *out, void *workspace, size_t workspace_bytes,
