@@ -167,6 +167,13 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def workspace(nbytes, device):
+    """A scratch buffer of at least `nbytes` (what an mdx_*_workspace_bytes() returned) for one launch: uint8, so hand it over
+    as ptr(ws, torch.uint8).  Whole 16-byte units and never empty; the base is aligned to 16 bytes and more, as every
+    allocation of torch's is (512 on the GPU, 64 on the host) -- the training kernel addresses it in 16-byte units."""
+    return torch.empty(max((int(nbytes) + 15) & ~15, 16), dtype=torch.uint8, device=device)
+
+
 def make_desc(B, H, W, h, w, S, automask, min_depth, max_depth):
     d = Desc()
     api.mdx_desc_init(C.byref(d), B, H, W, h, w, S, int(bool(automask)), min_depth, max_depth)

@@ -13,15 +13,21 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import api, ptr, stream
+from ._lib import api, ptr, stream, workspace
 
 
-def _f32c(t):
-    return t.contiguous().float() if (t.dtype != torch.float32 or not t.is_contiguous()) else t
+def _f32c(t, keep_format=False):
+    """A parameter or small tensor as contiguous float32 (itself when it already is); None passes.  keep_format: a dense
+    channels-last 4-D weight stays as it is -- the kernel is handed its strides."""
+    if t is not None and t.dtype != torch.float32:
+        t = t.float()
+    if t is None or t.is_contiguous() or (keep_format and t.is_contiguous(memory_format=torch.channels_last)):
+        return t
+    return t.contiguous()
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 8) // 8 + 1, dtype=torch.float64, device=device)
+def _byref(struct):
+    return C.byref(struct) if struct is not None else None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -130,14 +136,14 @@ class _PhotometricScale(torch.autograd.Function):
         reproj = torch.empty(B, S, H, W, device=dev, dtype=torch.float32) if cfg.get("need_reproj") else None
         coef = torch.empty(B, 9, H, W, device=dev, dtype=torch.float32) if keep_coef else None
         nws = api.mdx_photometric_workspace_bytes(C.byref(d))
-        ws = _ws(nws, dev)
+        ws = workspace(nws, dev)
         hook = _timing_hook("fwd") if keep_coef else None
         api.mdx_photometric_fwd_timed(
             C.byref(d), ptr(disp), ptr(target), C.byref(src), ptr(invK), ptr(P),
-            ptr(ident, optional=True) if automask else None, ptr(noise, optional=True) if automask else None,
+            ptr(ident) if automask else None, ptr(noise) if automask else None,
             ptr(idx, torch.uint8), ptr(loss_sum), ptr(to_opt, optional=True), ptr(depth, optional=True),
-            ptr(warp, optional=True), ptr(reproj, optional=True), ptr(coef, optional=True), ptr(ws, torch.float64),
-            nws, stream(), C.byref(hook) if hook is not None else None)
+            ptr(warp, optional=True), ptr(reproj, optional=True), ptr(coef, optional=True), ptr(ws, torch.uint8),
+            nws, stream(), _byref(hook))
         ctx.save_for_backward(disp, P, target, invK, idx, *sources)
         ctx.warp = warp if keep_warp else None
         ctx.coef = coef
@@ -159,12 +165,12 @@ class _PhotometricScale(torch.autograd.Function):
         gP = torch.empty(S, B, 3, 4, device=dev, dtype=torch.float32)
         g_dev = _f32c(g_sum.reshape(1))
         nws = api.mdx_photometric_workspace_bytes(C.byref(d))
-        ws = _ws(nws, dev)
+        ws = workspace(nws, dev)
         hook = _timing_hook("bwd") if ctx.coef is not None else None
         api.mdx_photometric_bwd_timed(
             C.byref(d), ptr(disp), ptr(target), C.byref(src), ptr(invK), ptr(P), ptr(idx, torch.uint8),
             ptr(ctx.warp, optional=True), ptr(ctx.coef, optional=True), 1.0, ptr(g_dev), ptr(gdisp), ptr(gP),
-            ptr(ws, torch.float64), nws, stream(), C.byref(hook) if hook is not None else None)
+            ptr(ws, torch.uint8), nws, stream(), _byref(hook))
         return (gdisp, gP, None, None, None, None, None) + (None,) * S
 
 
@@ -253,12 +259,11 @@ def _train_launch(cfg, target, invK, ident, noises, sources, Pl, disps):
     to_opt = [torch.empty(B, H, W, device=dev, dtype=torch.float32) for _ in range(nsc)] \
         if cfg.get("need_to_opt") else None
     nws = api.mdx_photometric_train_workspace_bytes(C.byref(d))
-    ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
+    ws = workspace(nws, dev)
     hook = _timing_hook("train" if grads else "eval")
-    tail = (_lib.ptr_array(idx, torch.uint8), ptr(sums), _lib.ptr_array(gdisp) if grads else None,
-            ptr(gP) if grads else None, ptr(depth0, optional=True),
-            _lib.ptr_array(to_opt) if to_opt is not None else None, ptr(ws, torch.float64), nws, stream(),
-            C.byref(hook) if hook is not None else None)
+    tail = (_lib.ptr_array(idx, torch.uint8), ptr(sums), _lib.ptr_array(gdisp) if grads else None, ptr(gP, optional=True),
+            ptr(depth0, optional=True), _lib.ptr_array(to_opt) if to_opt is not None else None, ptr(ws, torch.uint8), nws,
+            stream(), _byref(hook))
     if pre is not None:
         api.mdx_photometric_train_pre(
             C.byref(d), _lib.ptr_array(disps), ptr(target), C.byref(src), ptr(invK), _lib.ptr_array(Ps),
@@ -269,6 +274,18 @@ def _train_launch(cfg, target, invK, ident, noises, sources, Pl, disps):
             C.byref(d), _lib.ptr_array(disps), ptr(target), C.byref(src), ptr(invK), _lib.ptr_array(Ps),
             ptr(ident) if automask else None, _lib.ptr_array(noises) if automask else None, *tail)
     return dict(sums=sums, idx=idx, gdisp=gdisp, gP=gP, depth0=depth0, to_opt=to_opt, per_scale_P=per_scale_P, pixels=B * H * W)
+
+
+def _train_args(what, disps, P, noises, automask, min_depth, max_depth, need_depth, pre, **more):
+    """What photometric_train and train_loss do with their arguments before their node runs -> (the projections as a list: one,
+    or one per scale; the noises as a list or None; the cfg dict _train_launch reads, `more` included)."""
+    Pl = list(P) if isinstance(P, (list, tuple)) else [P]
+    if len(Pl) not in (1, len(disps)):
+        raise _lib.MdxError("%s: %d projections for %d scales (one, or one per scale)" % (what, len(Pl), len(disps)))
+    grads = torch.is_grad_enabled() and any(t.requires_grad for t in list(disps) + Pl)
+    cfg = dict(automask=bool(automask), min_depth=float(min_depth), max_depth=float(max_depth), need_depth=bool(need_depth),
+               grads=grads, pre=pre, **more)
+    return Pl, (None if noises is None else list(noises)), cfg
 
 
 class _PhotometricTrain(torch.autograd.Function):
@@ -308,16 +325,10 @@ def photometric_train(disps, P, target, sources, invK, ident=None, noises=None, 
     loads the target's window statistics and each pixel's best identity channel instead of re-deriving them per scale
     (ident / noises are not needed; same results bit for bit).  Returns dict: 'sums' [nscales] (differentiable: sum over pixels of
     to_optimise per scale), 'idx' (list of uint8 [B,H,W]), 'depth' (scale 0, optional), 'to_opt' (optional list)."""
-    Pl = list(P) if isinstance(P, (list, tuple)) else [P]
-    if len(Pl) not in (1, len(disps)):
-        raise _lib.MdxError("photometric_train: %d projections for %d scales (one, or one per scale)" % (len(Pl), len(disps)))
-    grads = torch.is_grad_enabled() and any(t.requires_grad for t in list(disps) + Pl)
-    cfg = dict(automask=bool(automask), min_depth=float(min_depth), max_depth=float(max_depth),
-               need_depth=bool(need_depth), need_to_opt=bool(need_to_opt), rows_per_chunk=int(rows_per_chunk),
-               grads=grads, pre=pre)
+    Pl, noises, cfg = _train_args("photometric_train", disps, P, noises, automask, min_depth, max_depth, need_depth, pre,
+                                  need_to_opt=bool(need_to_opt), rows_per_chunk=int(rows_per_chunk))
     n = len(disps)
-    out = _PhotometricTrain.apply(target, invK, ident, cfg, list(noises) if noises is not None else None,
-                                  list(sources), len(Pl), *Pl, *disps)
+    out = _PhotometricTrain.apply(target, invK, ident, cfg, noises, list(sources), len(Pl), *Pl, *disps)
     res = dict(sums=out[0], idx=list(out[1:1 + n]), depth=out[1 + n])
     res["to_opt"] = list(out[2 + n:2 + 2 * n]) if need_to_opt else None
     return res
@@ -333,9 +344,9 @@ class _SmoothLoss(torch.autograd.Function):
         need = ctx.needs_input_grad[0]
         g = torch.empty_like(disp) if need else None
         nws = api.mdx_smooth_workspace_bytes(B, h, w)
-        ws = _ws(nws, dev)
+        ws = workspace(nws, dev)
         api.mdx_smooth_loss(B, h, w, ptr(disp), ptr(color), int(normalize), ptr(loss), ptr(g, optional=True),
-                            ptr(ws, torch.float64), nws, stream())
+                            ptr(ws, torch.uint8), nws, stream())
         if need:
             ctx.save_for_backward(g)
         return loss.reshape(())
@@ -364,9 +375,9 @@ def _smooth_multi_launch(normalize, colors, disps, need):
     loss = torch.empty(n, device=dev, dtype=torch.float32)
     gs = [torch.empty_like(d) for d in disps] if need else None
     nws = api.mdx_smooth_multi_workspace_bytes(n, B, hs, ws_)
-    ws = _ws(nws, dev)
+    ws = workspace(nws, dev)
     api.mdx_smooth_loss_multi(n, B, hs, ws_, _lib.ptr_array(disps), _lib.ptr_array(colors), int(normalize),
-                              ptr(loss), _lib.ptr_array(gs) if need else None, ptr(ws, torch.float64), nws, stream())
+                              ptr(loss), _lib.ptr_array(gs) if need else None, ptr(ws, torch.uint8), nws, stream())
     return loss, gs
 
 
@@ -460,18 +471,12 @@ def train_loss(disps, P, target, sources, invK, colors, scales, disp_smoothness,
     every scale; scales: opt.scales.  Returns dict: 'loss' (scalar, differentiable), 'sums', 'smooth' [nscales], 'idx', 'depth'.
     The numbers are those of smooth_loss_multi + photometric_train + the reference's scalar ops, bit for bit (the projection
     gradient: the scales are summed in index order)."""
-    Pl = list(P) if isinstance(P, (list, tuple)) else [P]
-    if len(Pl) not in (1, len(disps)):
-        raise _lib.MdxError("train_loss: %d projections for %d scales (one, or one per scale)" % (len(Pl), len(disps)))
     if len(colors) != len(disps) or len(scales) != len(disps):
         raise _lib.MdxError("train_loss: %d disparities, %d colour maps, %d scales" % (len(disps), len(colors), len(scales)))
-    grads = torch.is_grad_enabled() and any(t.requires_grad for t in list(disps) + Pl)
-    cfg = dict(automask=bool(automask), min_depth=float(min_depth), max_depth=float(max_depth), need_depth=bool(need_depth),
-               need_to_opt=False, rows_per_chunk=0, grads=grads, pre=pre, scales=[int(v) for v in scales],
-               disp_smoothness=float(disp_smoothness), smooth=smooth)
+    Pl, noises, cfg = _train_args("train_loss", disps, P, noises, automask, min_depth, max_depth, need_depth, pre,
+                                  scales=[int(v) for v in scales], disp_smoothness=float(disp_smoothness), smooth=smooth)
     n = len(disps)
-    out = _TrainLoss.apply(target, invK, ident, cfg, list(noises) if noises is not None else None, list(sources),
-                           list(colors), len(Pl), *Pl, *disps)
+    out = _TrainLoss.apply(target, invK, ident, cfg, noises, list(sources), list(colors), len(Pl), *Pl, *disps)
     return dict(loss=out[0], sums=out[1], smooth=out[2], idx=list(out[3:3 + n]), depth=out[3 + n])
 
 
@@ -514,8 +519,7 @@ class _Disp2Depth(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gsd, gdepth):
         (disp,) = ctx.saved_tensors
-        gsd = _f32c(gsd) if gsd is not None else None
-        gdepth = _f32c(gdepth) if gdepth is not None else None
+        gsd, gdepth = _f32c(gsd), _f32c(gdepth)
         if gsd is None and gdepth is None:
             return None, None, None
         g = torch.empty_like(disp)
@@ -572,9 +576,9 @@ class _Project(torch.autograd.Function):
         gcam = torch.empty_like(cam)
         gP = torch.empty_like(P)
         nws = api.mdx_project_workspace_bytes(B, H, W)
-        ws = _ws(nws, cam.device)
+        ws = workspace(nws, cam.device)
         api.mdx_project_bwd(ptr(cam), ptr(P), ptr(ggrid), B, H, W, eps, ptr(gcam), ptr(gP),
-                            ptr(ws, torch.float64), nws, stream())
+                            ptr(ws, torch.uint8), nws, stream())
         return gcam, gP, None, None, None
 
 
@@ -691,14 +695,6 @@ _DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
 _CL = torch.channels_last
 
 
-def _glue_dtype(t, what):
-    if not t.is_cuda:
-        raise _lib.MdxError("%s needs CUDA tensors (the HIP path has no CPU fallback), got %s" % (what, t.device))
-    if t.dtype not in _DTYPE_CODE:
-        raise _lib.MdxError("%s supports float32 / bfloat16, got %s" % (what, t.dtype))
-    return _DTYPE_CODE[t.dtype]
-
-
 from .layout import is_channels_last  # noqa: E402,F401  (re-exported: the layout test every op below dispatches on)
 
 
@@ -708,14 +704,31 @@ def _nhwc_ok(dtype, *channels):
     return all(c % n == 0 for c in channels)
 
 
+def _layout(x, what, *channels):
+    """How the op `what` takes the GPU map x, whose kernels see these channel counts -> (dtype code, channels-last?, the outputs'
+    memory format).  Channels-last when x is and every count fills whole channel vectors; any other map takes the planar kernel."""
+    if not x.is_cuda:
+        raise _lib.MdxError("%s needs CUDA tensors (the HIP path has no CPU fallback), got %s" % (what, x.device))
+    if x.dtype not in _DTYPE_CODE:
+        raise _lib.MdxError("%s supports float32 / bfloat16, got %s" % (what, x.dtype))
+    cl = is_channels_last(x) and _nhwc_ok(x.dtype, *channels)
+    return _DTYPE_CODE[x.dtype], cl, (_CL if cl else torch.contiguous_format)
+
+
 def _as(t, cl):
+    if t is None:
+        return None
     return t.contiguous(memory_format=_CL) if cl else t.contiguous()
+
+
+def _cl_map(x, dtypes=_DTYPE_CODE):
+    """What every channels-last-only op below asks of its map."""
+    return x.is_cuda and x.dim() == 4 and x.dtype in dtypes and is_channels_last(x)
 
 
 class _DecoderGlue(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, skip, bias, elu, upsample, out_dtype):
-        in_code = _glue_dtype(raw, "decoder_glue")
         B, C1, h, w = raw.shape
         u = 2 if upsample else 1
         C2 = 0
@@ -724,31 +737,25 @@ class _DecoderGlue(torch.autograd.Function):
                 raise _lib.MdxError("decoder_glue: skip %s %s does not match raw %s %s (x%d)"
                                     % (tuple(skip.shape), skip.dtype, tuple(raw.shape), raw.dtype, u))
             C2 = skip.shape[1]
-        cl = is_channels_last(raw) and _nhwc_ok(raw.dtype, C1, C2)
-        raw = _as(raw, cl)
-        skip = _as(skip, cl) if skip is not None else None
-        if bias is not None:
-            bias = _f32c(bias)
-            if bias.shape != (C1,):
-                raise _lib.MdxError("decoder_glue: bias %s for %d channels" % (tuple(bias.shape), C1))
-        out = torch.empty(B, C1 + C2, u * h + 2, u * w + 2, device=raw.device, dtype=out_dtype,
-                          memory_format=_CL if cl else torch.contiguous_format)
+        in_code, cl, fmt = _layout(raw, "decoder_glue", C1, C2)
+        raw, skip, bias = _as(raw, cl), _as(skip, cl), _f32c(bias)
+        if bias is not None and bias.shape != (C1,):
+            raise _lib.MdxError("decoder_glue: bias %s for %d channels" % (tuple(bias.shape), C1))
+        out = torch.empty(B, C1 + C2, u * h + 2, u * w + 2, device=raw.device, dtype=out_dtype, memory_format=fmt)
         fn = api.mdx_decoder_glue_nhwc_fwd if cl else api.mdx_decoder_glue_fwd
-        fn(ptr(raw, raw.dtype, cl=cl), ptr(skip, raw.dtype, cl=cl) if skip is not None else None,
-           ptr(bias) if bias is not None else None, ptr(out, out_dtype, cl=cl), B, C1, C2, h, w,
-           int(upsample), int(elu), in_code, _DTYPE_CODE[out_dtype], stream())
+        fn(ptr(raw, raw.dtype, cl=cl), ptr(skip, raw.dtype, optional=True, cl=cl), ptr(bias, optional=True),
+           ptr(out, out_dtype, cl=cl), B, C1, C2, h, w, int(upsample), int(elu), in_code, _DTYPE_CODE[out_dtype], stream())
         ctx.save_for_backward(raw, bias)
-        ctx.meta = (C2, bool(elu), bool(upsample), out_dtype, cl)
+        ctx.meta = (C2, bool(elu), bool(upsample), out_dtype, cl, fmt)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         raw, bias = ctx.saved_tensors
-        C2, elu, upsample, out_dtype, cl = ctx.meta
+        C2, elu, upsample, out_dtype, cl, fmt = ctx.meta
         B, C1, h, w = raw.shape
         u = 2 if upsample else 1
         gout = _as(gout.to(out_dtype), cl)
-        fmt = _CL if cl else torch.contiguous_format
         graw = torch.empty_like(raw)
         gskip = torch.empty(B, C2, u * h, u * w, device=raw.device, dtype=raw.dtype, memory_format=fmt) if C2 else None
         dbias = ws = None
@@ -758,12 +765,11 @@ class _DecoderGlue(torch.autograd.Function):
             dbias = torch.empty(C1, device=raw.device, dtype=torch.float32)
             nws = (api.mdx_decoder_glue_nhwc_workspace_bytes(B, C1, h, w, code) if cl
                    else api.mdx_decoder_glue_workspace_bytes(B, C1, h, w))
-            ws = torch.empty(nws // 4 + 1, device=raw.device, dtype=torch.float32)
+            ws = workspace(nws, raw.device)
         fn = api.mdx_decoder_glue_nhwc_bwd if cl else api.mdx_decoder_glue_bwd
-        fn(ptr(gout, out_dtype, cl=cl), ptr(raw, raw.dtype, cl=cl), ptr(bias) if bias is not None else None,
-           ptr(graw, raw.dtype, cl=cl), ptr(gskip, raw.dtype, cl=cl) if C2 else None,
-           ptr(dbias) if bias is not None else None, B, C1, C2, h, w, int(upsample), int(elu), code,
-           _DTYPE_CODE[out_dtype], ptr(ws) if ws is not None else None, nws, stream())
+        fn(ptr(gout, out_dtype, cl=cl), ptr(raw, raw.dtype, cl=cl), ptr(bias, optional=True), ptr(graw, raw.dtype, cl=cl),
+           ptr(gskip, raw.dtype, optional=True, cl=cl), ptr(dbias, optional=True), B, C1, C2, h, w, int(upsample), int(elu), code,
+           _DTYPE_CODE[out_dtype], ptr(ws, torch.uint8, optional=True), nws, stream())
         return graw, gskip, dbias, None, None, None
 
 
@@ -784,13 +790,11 @@ def decoder_glue(raw, skip=None, elu=True, upsample=True, out_dtype=None, bias=N
 class _BiasAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, relu):
-        code = _glue_dtype(x, "bias_act")
         B, Cc, H, W = x.shape
         x = _as(x, True)
-        b32 = bias if bias.dtype == torch.float32 else bias.float()
         y = torch.empty_like(x)
-        api.mdx_bias_act_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32), ptr(y, x.dtype, cl=True), B, Cc, H, W, int(relu), code,
-                                  stream())
+        api.mdx_bias_act_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(_f32c(bias)), ptr(y, x.dtype, cl=True), B, Cc, H, W, int(relu),
+                                  _DTYPE_CODE[x.dtype], stream())
         ctx.save_for_backward(y)
         ctx.meta = (bool(relu), bias.dtype)
         return y
@@ -805,15 +809,15 @@ class _BiasAct(torch.autograd.Function):
         dx = torch.empty_like(y)
         db = torch.empty(Cc, device=y.device, dtype=torch.float32)
         nws = api.mdx_bias_act_nhwc_workspace_bytes(B, Cc, H, W, code)
-        ws = torch.empty(nws // 4 + 1, device=y.device, dtype=torch.float32)
+        ws = workspace(nws, y.device)
         api.mdx_bias_act_nhwc_bwd(ptr(dy, y.dtype, cl=True), ptr(y, y.dtype, cl=True), ptr(dx, y.dtype, cl=True), ptr(db), B, Cc,
-                                  H, W, int(relu), code, ptr(ws), nws, stream())
+                                  H, W, int(relu), code, ptr(ws, torch.uint8), nws, stream())
         return dx, db.to(bdt), None
 
 
 def bias_act_ok(x):
     """Can bias_act take this map?  (channels-last GPU map, float32 / bfloat16, whole 16-byte channel vectors.)"""
-    return (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPE_CODE and is_channels_last(x) and _nhwc_ok(x.dtype, x.shape[1]))
+    return _cl_map(x) and _nhwc_ok(x.dtype, x.shape[1])
 
 
 def bias_act(x, bias, relu=True):
@@ -828,13 +832,11 @@ def bias_act(x, bias, relu=True):
 class _MeanBias(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, scale):
-        code = _glue_dtype(x, "mean_bias")
         B, Cc, H, W = x.shape
         x = _as(x, True)
-        b32 = None if bias is None else (bias if bias.dtype == torch.float32 else bias.float())
         out = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
-        api.mdx_mean_bias_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(b32) if b32 is not None else None, ptr(out), B, Cc, H, W,
-                                   scale, code, stream())
+        api.mdx_mean_bias_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(_f32c(bias), optional=True), ptr(out), B, Cc, H, W, scale,
+                                   _DTYPE_CODE[x.dtype], stream())
         ctx.meta = (tuple(x.shape), x.dtype, float(scale), None if bias is None else bias.dtype)
         return out
 
@@ -844,15 +846,20 @@ class _MeanBias(torch.autograd.Function):
         g = _f32c(g)
         dx = torch.empty((B, Cc, H, W), device=g.device, dtype=dt, memory_format=_CL)
         db = torch.empty(Cc, device=g.device, dtype=torch.float32) if bdt is not None else None
-        api.mdx_mean_bias_nhwc_bwd(ptr(g), ptr(dx, dt, cl=True), ptr(db) if db is not None else None, B, Cc, H, W,
-                                   scale, _DTYPE_CODE[dt], stream())
+        api.mdx_mean_bias_nhwc_bwd(ptr(g), ptr(dx, dt, cl=True), ptr(db, optional=True), B, Cc, H, W, scale, _DTYPE_CODE[dt],
+                                   stream())
         return dx, (db.to(bdt) if db is not None else None), None
+
+
+def mean_bias_ok(x):
+    """Can mean_bias take this map?  (channels-last GPU map, float32 / bfloat16; any channel count.)"""
+    return _cl_map(x)
 
 
 def mean_bias(x, bias=None, scale=1.0):
     """scale * (x.mean((2, 3)) + bias) -> [B, C] float32 for a channels-last GPU map: the pose head's spatial mean and 0.01
     (pose_decoder.py:51-53) behind a convolution that ran without its bias.  One launch each way."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPE_CODE and is_channels_last(x)):
+    if not mean_bias_ok(x):
         raise _lib.MdxError("mean_bias: needs a channels-last GPU map, got %s %s" % (tuple(x.shape), x.dtype))
     return _MeanBias.apply(x, bias, float(scale))
 
@@ -913,18 +920,18 @@ class _ThinConv3x3(torch.autograd.Function):
             gy = _as(gy, True)
             gw = torch.empty_like(weight)
             nws = api.mdx_thin_conv3x3_wgrad_workspace_bytes(B, Cin, 16, Hp - 2, Wp - 2)
-            ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
+            ws = workspace(nws, x.device)
             api.mdx_thin_conv3x3_wgrad(ptr(x, cl=True), ptr(gy, cl=True), ptr(gw, cl="any"), gw.stride(0), gw.stride(1),
-                                       gw.stride(2), gw.stride(3), B, Cin, 16, Hp - 2, Wp - 2, ptr(ws), nws, stream())
+                                       gw.stride(2), gw.stride(3), B, Cin, 16, Hp - 2, Wp - 2, ptr(ws, torch.uint8), nws, stream())
         return gx, gw
 
 
 def thin_conv_ok(x, weight):
     """A 3x3 convolution thin_conv3x3 takes: float32 channels-last GPU map [B,Cin,h+2,w+2] with Cin 16 or 32, weight [16,Cin,3,3]
     (dense, either memory format), w a multiple of 4, no autocast."""
-    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32 and is_channels_last(x)
-            and tuple(weight.shape) == (16, x.shape[1], 3, 3) and x.shape[1] in (16, 32) and x.shape[3] > 2 and (x.shape[3] - 2) % 4 == 0
-            and x.shape[2] > 2 and (weight.is_contiguous() or weight.is_contiguous(memory_format=_CL)) and not torch.is_autocast_enabled())
+    return (_cl_map(x, (torch.float32,)) and weight.dtype == torch.float32 and tuple(weight.shape) == (16, x.shape[1], 3, 3)
+            and x.shape[1] in (16, 32) and x.shape[3] > 2 and (x.shape[3] - 2) % 4 == 0 and x.shape[2] > 2
+            and (weight.is_contiguous() or weight.is_contiguous(memory_format=_CL)) and not torch.is_autocast_enabled())
 
 
 def thin_conv3x3(x, weight):
@@ -940,17 +947,13 @@ def thin_conv3x3(x, weight):
 class _DispHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
-        code = _glue_dtype(x, "disp_head")
         B, Cc, Hp, Wp = x.shape
         x = _as(x, True)
-        w32 = weight if weight.dtype == torch.float32 else weight.float()
-        if not (w32.is_contiguous() or w32.is_contiguous(memory_format=torch.channels_last)):
-            w32 = w32.contiguous()
-        b32 = None if bias is None else (bias if bias.dtype == torch.float32 else bias.float())
+        w32 = _f32c(weight, keep_format=True)
         disp = torch.empty(B, 1, Hp - 2, Wp - 2, device=x.device, dtype=torch.float32)
         _, sc, sy, sx = w32.stride()
-        api.mdx_disp_head_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), sc, sy, sx, ptr(b32) if b32 is not None else None,
-                                   ptr(disp), B, Cc, Hp - 2, Wp - 2, code, stream())
+        api.mdx_disp_head_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), sc, sy, sx, ptr(_f32c(bias), optional=True),
+                                   ptr(disp), B, Cc, Hp - 2, Wp - 2, _DTYPE_CODE[x.dtype], stream())
         ctx.save_for_backward(x, w32, disp)
         ctx.meta = (weight.dtype, None if bias is None else bias.dtype)
         return disp
@@ -966,18 +969,18 @@ class _DispHead(torch.autograd.Function):
         gw = torch.empty_like(w32)                     # the weight's own strides
         gb = torch.empty(1, device=x.device, dtype=torch.float32) if bdt is not None else None
         nws = api.mdx_disp_head_nhwc_workspace_bytes(B, Cc, Hp - 2, Wp - 2, code)
-        ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
+        ws = workspace(nws, x.device)
         _, sc, sy, sx = w32.stride()
         api.mdx_disp_head_nhwc_bwd(ptr(x, x.dtype, cl=True), ptr(w32, cl="any"), sc, sy, sx, ptr(g), ptr(disp),
-                                   ptr(gx, x.dtype, cl=True), ptr(gw, cl="any"), ptr(gb) if gb is not None else None, B, Cc,
-                                   Hp - 2, Wp - 2, code, ptr(ws), nws, stream())
+                                   ptr(gx, x.dtype, cl=True), ptr(gw, cl="any"), ptr(gb, optional=True), B, Cc,
+                                   Hp - 2, Wp - 2, code, ptr(ws, torch.uint8), nws, stream())
         return gx, gw.to(wdt), (gb.to(bdt) if gb is not None else None)
 
 
 def disp_head_ok(x, weight):
     """Can disp_head take this padded map and this head's weight?  (channels-last GPU map, one output channel, 3x3, a channel count
     that is a power of two from 4 to 256.)"""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPE_CODE and is_channels_last(x)):
+    if not _cl_map(x):
         return False
     n = 4                                  # channels per thread, either dtype (csrc/disp_head_nhwc.hip: DH_N)
     lp = x.shape[1] // n
@@ -998,12 +1001,10 @@ def disp_head(x, weight, bias=None):
 class _MaxPool3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, fork):
-        code = _glue_dtype(x, "maxpool3s2")
         B, Cc, H, W = x.shape
-        cl = is_channels_last(x) and _nhwc_ok(x.dtype, Cc)
+        code, cl, fmt = _layout(x, "maxpool3s2", Cc)
         x = _as(x, cl)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        fmt = _CL if cl else torch.contiguous_format
         out = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=x.dtype, memory_format=fmt)
         arg = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=torch.uint8, memory_format=fmt)
         if cl:
@@ -1013,21 +1014,21 @@ class _MaxPool3s2(torch.autograd.Function):
             api.mdx_maxpool3s2_fwd(ptr(x, x.dtype), ptr(out, x.dtype), ptr(arg, torch.uint8), B * Cc, H, W, code,
                                    stream())
         ctx.save_for_backward(arg)
-        ctx.meta = (H, W, x.dtype, cl)
+        ctx.meta = (H, W, x.dtype, cl, fmt)
         ctx.set_materialize_grads(False)
         return (out, out.view_as(out)) if fork else out
 
     @staticmethod
     def backward(ctx, gout, gout2=None):
         (arg,) = ctx.saved_tensors
-        H, W, dtype, cl = ctx.meta
+        H, W, dtype, cl, fmt = ctx.meta
         B, Cc = arg.shape[:2]
         gout, gout2 = _two_grads(gout, gout2, dtype, cl, fused_add=cl)
         if gout is None:
             return None, None
-        gin = torch.empty(B, Cc, H, W, device=gout.device, dtype=dtype, memory_format=_CL if cl else torch.contiguous_format)
+        gin = torch.empty(B, Cc, H, W, device=gout.device, dtype=dtype, memory_format=fmt)
         if cl:
-            api.mdx_maxpool3s2_nhwc_bwd(ptr(gout, dtype, cl=True), ptr(gout2, dtype, cl=True) if gout2 is not None else None,
+            api.mdx_maxpool3s2_nhwc_bwd(ptr(gout, dtype, cl=True), ptr(gout2, dtype, optional=True, cl=True),
                                         ptr(arg, torch.uint8, cl=True), ptr(gin, dtype, cl=True), B, Cc, H, W,
                                         _DTYPE_CODE[dtype], stream())
         else:
@@ -1055,6 +1056,12 @@ def maxpool3s2(x, fork=False):
 
 
 # ---- training-mode BatchNorm2d fused with residual add and ReLU (csrc/norm.hip, csrc/norm_nhwc.hip) ---------------
+def _residual(what, res, x):
+    if res is not None and (res.shape != x.shape or res.dtype != x.dtype):
+        raise _lib.MdxError("%s: residual %s %s does not match x %s %s" % (what, tuple(res.shape), res.dtype, tuple(x.shape), x.dtype))
+    return res
+
+
 class _BnAct(torch.autograd.Function):
     """groups > 1: the batch is `groups` consecutive sub-batches, each normalised with its own statistics and the
     running statistics updated once per sub-batch, in order -- exactly what `groups` separate calls of the module
@@ -1062,29 +1069,22 @@ class _BnAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, groups, fork):
-        code = _glue_dtype(x, "bn_act")
         B, Cc, H, W = x.shape
+        code, cl, _ = _layout(x, "bn_act", Cc)
         if B % groups:
             raise _lib.MdxError("bn_act: batch %d is not divisible into %d groups" % (B, groups))
-        cl = is_channels_last(x) and _nhwc_ok(x.dtype, Cc)
-        x = _as(x, cl)
-        if res is not None:
-            if res.shape != x.shape or res.dtype != x.dtype:
-                raise _lib.MdxError("bn_act: residual %s %s does not match x %s %s"
-                                    % (tuple(res.shape), res.dtype, tuple(x.shape), x.dtype))
-            res = _as(res, cl)
+        x, res = _as(x, cl), _as(_residual("bn_act", res, x), cl)
         weight, bias = _f32c(weight), _f32c(bias)
         y = torch.empty_like(x)
         save_mean = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
         save_invstd = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
         Bg = B // groups
         nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code) if cl else api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
-        ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
+        ws = workspace(nws, x.device)
         fn = api.mdx_bn_act_nhwc_fwd if cl else api.mdx_bn_act_fwd
-        fn(ptr(x, x.dtype, cl=cl), ptr(res, x.dtype, cl=cl) if res is not None else None, ptr(weight), ptr(bias),
-           ptr(running_mean) if running_mean is not None else None,
-           ptr(running_var) if running_var is not None else None, ptr(y, x.dtype, cl=cl), ptr(save_mean),
-           ptr(save_invstd), Bg, Cc, H, W, groups, eps, momentum, int(relu), code, ptr(ws), nws, stream())
+        fn(ptr(x, x.dtype, cl=cl), ptr(res, x.dtype, optional=True, cl=cl), ptr(weight), ptr(bias),
+           ptr(running_mean, optional=True), ptr(running_var, optional=True), ptr(y, x.dtype, cl=cl), ptr(save_mean),
+           ptr(save_invstd), Bg, Cc, H, W, groups, eps, momentum, int(relu), code, ptr(ws, torch.uint8), nws, stream())
         # channels-last float32, ReLU, no residual: backward re-derives the ReLU mask from x (y is not read: one map less per pass;
         # 760.3 -> 765.4 images/s.  bfloat16 maps: 1498 -> 1492 -- the re-derivation costs more than half a map of traffic)
         mask_from_x = cl and bool(relu) and res is None and x.dtype == torch.float32
@@ -1101,10 +1101,9 @@ class _BnAct(torch.autograd.Function):
         bias = None
         if mask_from_x:
             y, bias = None, y
-        none = (None,) * 11
         dy, dy2 = _two_grads(dy, dy2, x.dtype, cl, fused_add=cl)
         if dy is None:
-            return none
+            return (None,) * 11
         B, Cc, H, W = x.shape
         Bg = B // groups
         code = _DTYPE_CODE[x.dtype]
@@ -1112,22 +1111,19 @@ class _BnAct(torch.autograd.Function):
         dres = torch.empty_like(x) if has_res else None
         dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(Cc, device=x.device, dtype=torch.float32)
+        nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code) if cl else api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
+        ws = workspace(nws, x.device)
         if cl:
-            nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code)
-            ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
             api.mdx_bn_act_nhwc_bwd(
-                ptr(dy, x.dtype, cl=True), ptr(dy2, x.dtype, cl=True) if dy2 is not None else None,
-                ptr(y, x.dtype, cl=True) if y is not None else None, ptr(x, x.dtype, cl=True), ptr(weight),
-                ptr(bias) if bias is not None else None, ptr(save_mean), ptr(save_invstd), ptr(dx, x.dtype, cl=True),
-                ptr(dres, x.dtype, cl=True) if has_res else None, ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups, int(relu),
-                code, ptr(ws), nws, stream())
+                ptr(dy, x.dtype, cl=True), ptr(dy2, x.dtype, optional=True, cl=True), ptr(y, x.dtype, optional=True, cl=True),
+                ptr(x, x.dtype, cl=True), ptr(weight), ptr(bias, optional=True), ptr(save_mean), ptr(save_invstd),
+                ptr(dx, x.dtype, cl=True), ptr(dres, x.dtype, optional=True, cl=True), ptr(dgamma), ptr(dbeta), Bg, Cc, H, W,
+                groups, int(relu), code, ptr(ws, torch.uint8), nws, stream())
         else:
-            nws = api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
-            ws = torch.empty(nws // 4 + 1, device=x.device, dtype=torch.float32)
             api.mdx_bn_act_bwd(
                 ptr(dy, x.dtype), ptr(y, x.dtype), ptr(x, x.dtype), ptr(weight), ptr(save_mean), ptr(save_invstd),
-                ptr(dx, x.dtype), ptr(dres, x.dtype) if has_res else None, ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups,
-                int(relu), code, ptr(ws), nws, stream())
+                ptr(dx, x.dtype), ptr(dres, x.dtype, optional=True), ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups,
+                int(relu), code, ptr(ws, torch.uint8), nws, stream())
         return (dx, dres, dgamma, dbeta) + (None,) * 7
 
 
@@ -1151,18 +1147,12 @@ def bn_act_infer(x, weight, bias, running_mean, running_var, eps=1e-5, residual=
     takes the planar one).  The statistics are read, never written.  float32 or bfloat16 activations, float32 parameters.
     No autograd node: for callers that need no gradient (torch.no_grad(), or an input that does not require one).
     fork: the result twice, as bn_act returns it."""
-    code = _glue_dtype(x, "bn_act_infer")
     B, Cc, H, W = x.shape
-    cl = is_channels_last(x) and _nhwc_ok(x.dtype, Cc)
-    x = _as(x, cl)
-    if residual is not None:
-        if residual.shape != x.shape or residual.dtype != x.dtype:
-            raise _lib.MdxError("bn_act_infer: residual %s %s does not match x %s %s"
-                                % (tuple(residual.shape), residual.dtype, tuple(x.shape), x.dtype))
-        residual = _as(residual, cl)
+    code, cl, _ = _layout(x, "bn_act_infer", Cc)
+    x, residual = _as(x, cl), _as(_residual("bn_act_infer", residual, x), cl)
     y = torch.empty_like(x)
     fn = api.mdx_bn_act_nhwc_infer if cl else api.mdx_bn_act_infer
-    fn(ptr(x, x.dtype, cl=cl), ptr(residual, x.dtype, cl=cl) if residual is not None else None, ptr(_f32c(weight)),
+    fn(ptr(x, x.dtype, cl=cl), ptr(residual, x.dtype, optional=True, cl=cl), ptr(_f32c(weight)),
        ptr(_f32c(bias)), ptr(_f32c(running_mean)), ptr(_f32c(running_var)), ptr(y, x.dtype, cl=cl), B, Cc, H, W, float(eps),
        int(bool(relu)), code, stream())
     return (y, y.view_as(y)) if fork else y
@@ -1222,8 +1212,7 @@ class _PoseProjection(torch.autograd.Function):
         graw = torch.empty_like(raw)
         sel = tuple((C.c_int32 * S)(*a) for a in (row0, frame, invert))
         api.mdx_pose_projection_bwd(ptr(raw), M, F, ptr(K), B, S, *sel,
-                                    ptr(_f32c(gP)) if gP is not None else None,
-                                    ptr(_f32c(gT)) if gT is not None else None, ptr(graw), stream())
+                                    ptr(_f32c(gP), optional=True), ptr(_f32c(gT), optional=True), ptr(graw), stream())
         return graw, None, None, None, None, None
 
 
@@ -1253,7 +1242,7 @@ def depth_monitor(pred, gt, window, min_depth=1e-3, max_depth=80.0):
     r0, r1, c0, c1 = (int(v) for v in window)
     out = torch.empty(8, device=pred.device, dtype=torch.float32)
     nws = api.mdx_depth_monitor_workspace_bytes(B, r0, r1, c0, c1)
-    ws = _ws(nws, pred.device)
+    ws = workspace(nws, pred.device)
     api.mdx_depth_monitor(ptr(pred), B, h, w, ptr(gt), gh, gw, r0, r1, c0, c1, min_depth, max_depth, ptr(out),
-                          ptr(ws, torch.float64), nws, stream())
+                          ptr(ws, torch.uint8), nws, stream())
     return out

@@ -3,15 +3,18 @@
     forward_depth   processor.py:33-55      forward_pose   processor.py:58-136
     image2warping   processor.py:139-163    compute_loss   processor.py:166-218
 
-With opt.fused (default) image2warping only forms the projection matrices.  compute_loss then runs, when gradients
-are wanted (training), ONE gfx950 kernel for all scales that evaluates the photometric term AND its gradient
-(opt.fused_train, default: mdx.functional.photometric_train, csrc/photo_train.hip); without gradients
-(validation) or with opt.fused_train = False one fused forward kernel per scale (+ one backward kernel per scale).
-The identity losses, which do not depend on the scale, are evaluated once per step.  With opt.fused = False the
-reference's op-by-op sequence runs on the fine-grained kernels and every reference output key is populated
-(("warp_color", f, s), ...).  Results are identical between the modes.
+With opt.fused (default) image2warping only forms the projection matrices, and compute_loss takes one of three fused paths
+(compute.loss_path is the table).  Default: ONE gfx950 kernel for all scales that evaluates the photometric term AND its
+gradient -- under torch.no_grad() (validation) the same launch in its forward-only form -- inside one autograd node that also
+holds the smoothness launches and the scalar tail (mdx.functional.train_loss, csrc/photo_train.hip, csrc/loss_total.hip).
+opt.fused_tail = False: the same kernel (mdx.functional.photometric_train) followed by the reference's scalar ops.
+opt.fused_train = False, or more than 4 scales: one fused forward kernel per scale (+ one backward kernel per scale).  What does
+not depend on the scale (identity losses, noise, the target's window statistics) is evaluated once per step.  With opt.fused =
+False, or on a CPU device, the reference's op-by-op sequence runs on the fine-grained ops and every reference output key is
+populated (("warp_color", f, s), ...).  Results are identical between the modes.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -287,7 +290,6 @@ class compute(object):
         steps taken: the finishing kernel of every step advances it).  Part of the run's state: control.save stores the
         offset, control.resume puts it back (set_noise_offset), graphed_step's warm-up restores it."""
         if self._rng is None:
-            import os
             self._rng = F.noise_state(device or self.device, stream=int(_opt(self.opt, "noise_stream", os.environ.get("RANK", "0"))))
             if getattr(self, "_rng_offset0", None) is not None:
                 self._rng.tensor[1] = int(self._rng_offset0)
@@ -315,8 +317,8 @@ class compute(object):
         (one-launch training kernel, fused tail, in-kernel noise)."""
         opt = self.opt
         target = inputs[("color", 0, 0)]
-        if not (self.fused and self.fused_train and self.fused_tail and self.prologue and len(opt.scales) <= 4 and target.is_cuda
-                and torch.is_grad_enabled() and all(("disp", s) in outputs for s in opt.scales)):
+        if not (self.loss_path(target) == self._loss_one_node and self.prologue and torch.is_grad_enabled()
+                and all(("disp", s) in outputs for s in opt.scales)):
             return
         automask = bool(opt.use_automasking)
         if automask and (self.noise_mode == "cpu" or any(("noise", s) in inputs for s in opt.scales)):
@@ -329,115 +331,134 @@ class compute(object):
         smooth = F.smooth_launch(disps, [inputs[("color", 0, s)] for s in opt.scales], need_grad=any(d.requires_grad for d in disps))
         outputs[("loss_prologue",)] = dict(pre=pre, smooth=smooth)
 
+    def loss_path(self, target):
+        """The method compute_loss runs: the first row that matches.  `fused` is self.fused: opt.fused, and False on a CPU device
+        (__init__); opt.fused_tail counts only with it.
+
+            fused   fused_train   len(scales) <= 4   fused_tail   target.is_cuda    path
+            no      .             .                  .            .                 _loss_op_by_op
+            yes     yes           yes                yes          yes               _loss_one_node
+            yes     yes           yes                .            .                 _loss_one_launch
+            yes     .             .                  .            .                 _loss_per_scale
+        """
+        one_launch = self.fused_train and len(self.opt.scales) <= 4
+        if not self.fused:
+            return self._loss_op_by_op
+        if one_launch and self.fused_tail and target.is_cuda:
+            return self._loss_one_node
+        return self._loss_one_launch if one_launch else self._loss_per_scale
+
     def compute_loss(self, inputs, outputs, setting):
         opt = self.opt
         target = inputs[("color", 0, 0)]
         sources = [inputs[("color", f, 0)] for f in opt.frame_ids[1:]]
-        S = len(sources)
         B, _, H, W = target.shape
-        automask = bool(opt.use_automasking)
-        total_loss = 0
-        ident = None
-        one_launch = self.fused and self.fused_train and len(opt.scales) <= 4
-        if self.fused and automask and not one_launch:
-            ident = F.identity_loss(target, sources)          # once per step (scale-independent)
-        # training: every scale's photometric term and its gradient in one launch (posecnn: one projection per scale);
-        # validation / torch.no_grad(): the same launch in its forward-only form.  What the scales share -- identity
-        # losses + noise + their minimum, the target's window statistics -- comes from ONE prologue launch
-        # (csrc/photo_prologue.hip); the noise is drawn inside it (the reference's host-side torch.randn with --noise cpu,
-        # or tensors injected by the parity tests, are handed to it instead)
-        train = None
-        smooth_all = None
-        if one_launch:
-            nsc = len(opt.scales)
-            noises = None
-            if automask:
-                if all(("noise", s) in inputs for s in opt.scales):     # injected (parity tests)
-                    noises = [inputs[("noise", s)] for s in opt.scales]
-                elif self.noise_mode == "cpu":
-                    noises = list(self._noise((nsc, B, S, H, W)).unbind(0))
-                elif self.prologue:
-                    self.noise_rng(target.device)
-            pre = None
-            early = outputs.pop(("loss_prologue",), None)          # loss_prologue() ran ahead of the pose stream's join
-            if early is not None:
-                pre = early["pre"]
-            elif self.prologue:
-                pre = F.photometric_prologue(target, sources, nsc, noises=noises, rng=self._rng, automask=automask)
-            elif automask:
-                ident = F.identity_loss(target, sources)
-                if noises is None:
-                    noises = list(torch.randn((nsc, B, S, H, W), device=self.device).unbind(0))
-            # The smoothness launches go BETWEEN the prologue and the training kernel (they depend on neither).  Launched right
-            # behind the prologue -- which writes 80 MB in 44 us -- the training kernel runs 17 % longer (223 us against 190 us,
-            # same code, same data: profiles/r04_load_latency.txt); two short launches in between and it does not.
-            if self.fused_tail and target.is_cuda:
-                # smoothness, photometric term and the scalar tail of processor.py:208-217 as one autograd node: one launch
-                # finishes the scalar, one launch in backward writes every scale's disparity gradient (mdx/functional.py: _TrainLoss)
-                res = F.train_loss([outputs[("disp", s)].float() for s in opt.scales],
-                                   (outputs[("P", opt.scales[0])] if opt.pose_type != "posecnn"
-                                    else [outputs[("P", s)] for s in opt.scales]),
-                                   target, sources, inputs[("inv_K", 0)], [inputs[("color", 0, s)] for s in opt.scales],
-                                   opt.scales, opt.disp_smoothness, ident, noises if pre is None else None,
-                                   automask=automask, min_depth=opt.min_depth, max_depth=opt.max_depth,
-                                   need_depth=(opt.scales[0] == 0), pre=pre, smooth=early["smooth"] if early is not None else None)
-                if res["depth"] is not None:
-                    outputs[("depth", 0, 0)] = res["depth"]
-                for k, scale in enumerate(opt.scales):
-                    outputs[("automask", scale)] = res["idx"][k]
-                outputs["loss"] = res["loss"]
-                return outputs
-            if self.fused and target.is_cuda:
-                smooth_all = F.smooth_loss_multi([outputs[("disp", s)].float() for s in opt.scales],
-                                                 [inputs[("color", 0, s)] for s in opt.scales])
-            train = F.photometric_train([outputs[("disp", s)].float() for s in opt.scales],
-                                        (outputs[("P", opt.scales[0])] if opt.pose_type != "posecnn"
-                                         else [outputs[("P", s)] for s in opt.scales]),
-                                        target, sources, inputs[("inv_K", 0)], ident, noises if pre is None else None,
-                                        automask=automask, min_depth=opt.min_depth, max_depth=opt.max_depth,
-                                        need_depth=(opt.scales[0] == 0), pre=pre)
-            if train["depth"] is not None:
-                outputs[("depth", 0, 0)] = train["depth"]
-        # fused mode: the smoothness term of every scale with each of its passes launched once (2 launches, not 16)
-        if smooth_all is None and self.fused and len(opt.scales) <= 4 and target.is_cuda:
-            smooth_all = F.smooth_loss_multi([outputs[("disp", s)].float() for s in opt.scales],
-                                             [inputs[("color", 0, s)] for s in opt.scales])
-        for k, scale in enumerate(opt.scales):
-            disp = outputs[("disp", scale)].float()
-            color = inputs[("color", 0, scale)]
-            if train is not None:
-                mean_min = train["sums"][k] / float(B * H * W)
-                outputs[("automask", scale)] = train["idx"][k]
-            elif self.fused:
-                noise = self._noise((B, S, H, W)) if automask else None
-                if ("noise", scale) in inputs:                 # injected (parity tests)
-                    noise = inputs[("noise", scale)]
-                res = F.photometric_scale(disp, outputs[("P", scale)], target, sources, inputs[("inv_K", 0)],
-                                          ident, noise, automask=automask, min_depth=opt.min_depth,
-                                          max_depth=opt.max_depth, need_depth=(scale == 0))
-                mean_min = res["sum"][0] / float(B * H * W)
-                outputs[("automask", scale)] = res["idx"]
-                if res["depth"] is not None:
-                    outputs[("depth", 0, scale)] = res["depth"]
-            else:
-                reprojection_loss = torch.cat([setting.loss["reprojection"](
-                    outputs[("warp_color", f, scale)], target) for f in opt.frame_ids[1:]], 1)
-                if automask:
-                    identity_loss = torch.cat([setting.loss["reprojection"](s, target) for s in sources], 1)
-                    noise = inputs[("noise", scale)] if ("noise", scale) in inputs else self._noise(identity_loss.shape)
-                    identity_loss = identity_loss + 0.00001 * noise
-                    combined_loss = torch.cat((identity_loss, reprojection_loss), dim=1)
-                else:
-                    combined_loss = reprojection_loss
-                if combined_loss.shape[1] == 1:
-                    to_optimise = combined_loss
-                else:
-                    to_optimise, idxs = torch.min(combined_loss, dim=1)
-                    outputs[("automask", scale)] = idxs
-                mean_min = to_optimise.mean()
-            smooth_loss = smooth_all[k] if smooth_all is not None else setting.loss["edge_aware"](disp=disp, color=color)
-            scale_loss = mean_min + opt.disp_smoothness * smooth_loss / (2 ** scale)
-            total_loss = total_loss + scale_loss
-        total_loss = total_loss / len(opt.scales)
-        outputs["loss"] = total_loss
+        # what the paths share
+        s = SimpleNamespace(target=target, sources=sources, shape=(B, len(sources), H, W), pixels=float(B * H * W),
+                            disps=[outputs[("disp", k)].float() for k in opt.scales],
+                            colors=[inputs[("color", 0, k)] for k in opt.scales], automask=bool(opt.use_automasking))
+        if self.fused:
+            s.photo = dict(automask=s.automask, min_depth=opt.min_depth, max_depth=opt.max_depth)
+            # one projection shared by the scales, or (posecnn) one per scale
+            s.P = outputs[("P", opt.scales[0])] if opt.pose_type != "posecnn" else [outputs[("P", k)] for k in opt.scales]
+            # the smoothness term of every scale with each of its passes launched once (2 launches, not 16)
+            s.smooth_multi = len(opt.scales) <= 4 and target.is_cuda
+        outputs["loss"] = self.loss_path(target)(s, inputs, outputs, setting)
         return outputs
+
+    def _scalar_tail(self, s, setting, mean_min, smooth_all):
+        """processor.py:208-217 around a path's mean_min(k, scale).  smooth_all: every scale's smoothness term
+        (F.smooth_loss_multi), or None: the reference's op, scale by scale."""
+        total_loss = 0
+        for k, scale in enumerate(self.opt.scales):
+            mean = mean_min(k, scale)
+            smooth_loss = smooth_all[k] if smooth_all is not None else setting.loss["edge_aware"](disp=s.disps[k], color=s.colors[k])
+            total_loss = total_loss + (mean + self.opt.disp_smoothness * smooth_loss / (2 ** scale))
+        return total_loss / len(self.opt.scales)
+
+    def _step_shared(self, s, inputs, outputs):
+        """What the scales of the one-launch paths share -- identity losses + noise + their minimum, the target's window
+        statistics -- from ONE prologue launch (csrc/photo_prologue.hip); the noise is drawn inside it (the reference's host-side
+        torch.randn with --noise cpu, or tensors injected by the parity tests, are handed to it instead).
+        -> (the training kernel's keyword arguments, the smoothness launches where loss_prologue() issued them already)."""
+        opt = self.opt
+        nsc = len(opt.scales)
+        noises = ident = pre = None
+        if s.automask:
+            if all(("noise", k) in inputs for k in opt.scales):     # injected (parity tests)
+                noises = [inputs[("noise", k)] for k in opt.scales]
+            elif self.noise_mode == "cpu":
+                noises = list(self._noise((nsc,) + s.shape).unbind(0))
+            elif self.prologue:
+                self.noise_rng(s.target.device)
+        early = outputs.pop(("loss_prologue",), None) or {}          # loss_prologue() ran ahead of the pose stream's join
+        if early:
+            pre = early["pre"]
+        elif self.prologue:
+            pre = F.photometric_prologue(s.target, s.sources, nsc, noises=noises, rng=self._rng, automask=s.automask)
+        elif s.automask:
+            ident = F.identity_loss(s.target, s.sources)
+            if noises is None:
+                noises = list(torch.randn((nsc,) + s.shape, device=self.device).unbind(0))
+        return dict(s.photo, ident=ident, noises=noises if pre is None else None, pre=pre,
+                    need_depth=(opt.scales[0] == 0)), early.get("smooth")
+
+    def _keep(self, outputs, res):
+        if res["depth"] is not None:
+            outputs[("depth", 0, 0)] = res["depth"]
+        for k, scale in enumerate(self.opt.scales):
+            outputs[("automask", scale)] = res["idx"][k]
+
+    def _loss_one_node(self, s, inputs, outputs, setting):
+        """Smoothness, photometric term and the scalar tail as one autograd node: one launch finishes the scalar, one launch in
+        backward writes every scale's disparity gradient (mdx/functional.py: _TrainLoss)."""
+        kw, smooth = self._step_shared(s, inputs, outputs)
+        res = F.train_loss(s.disps, s.P, s.target, s.sources, inputs[("inv_K", 0)], s.colors, self.opt.scales,
+                           self.opt.disp_smoothness, smooth=smooth, **kw)
+        self._keep(outputs, res)
+        return res["loss"]
+
+    def _loss_one_launch(self, s, inputs, outputs, setting):
+        """Every scale's photometric term and its gradient in ONE launch (posecnn: one projection per scale; under
+        torch.no_grad() the same launch in its forward-only form), then the reference's scalar ops."""
+        kw, _ = self._step_shared(s, inputs, outputs)
+        # The smoothness launches go BETWEEN the prologue and the training kernel (they depend on neither).  Launched right
+        # behind the prologue -- which writes 80 MB in 44 us -- the training kernel runs 17 % longer (223 us against 190 us,
+        # same code, same data: profiles/r04_load_latency.txt); two short launches in between and it does not.
+        # (F.train_loss places them the same way for _loss_one_node.)
+        smooth_all = F.smooth_loss_multi(s.disps, s.colors) if s.smooth_multi else None
+        train = F.photometric_train(s.disps, s.P, s.target, s.sources, inputs[("inv_K", 0)], **kw)
+        self._keep(outputs, train)
+        return self._scalar_tail(s, setting, lambda k, scale: train["sums"][k] / s.pixels, smooth_all)
+
+    def _loss_per_scale(self, s, inputs, outputs, setting):
+        """One fused forward kernel per scale (+ one backward kernel per scale): opt.fused_train = False, or more than 4 scales."""
+        ident = F.identity_loss(s.target, s.sources) if s.automask else None          # once per step (scale-independent)
+        smooth_all = F.smooth_loss_multi(s.disps, s.colors) if s.smooth_multi else None
+
+        def mean_min(k, scale):
+            noise = inputs.get(("noise", scale))                 # injected (parity tests)
+            if noise is None and s.automask:
+                noise = self._noise(s.shape)
+            res = F.photometric_scale(s.disps[k], outputs[("P", scale)], s.target, s.sources, inputs[("inv_K", 0)], ident, noise,
+                                      need_depth=(scale == 0), **s.photo)
+            outputs[("automask", scale)] = res["idx"]
+            if res["depth"] is not None:
+                outputs[("depth", 0, scale)] = res["depth"]
+            return res["sum"][0] / s.pixels
+        return self._scalar_tail(s, setting, mean_min, smooth_all)
+
+    def _loss_op_by_op(self, s, inputs, outputs, setting):
+        """The reference's sequence (processor.py:172-217) on the fine-grained ops, from image2warping's ("warp_color", f, scale)."""
+        def mean_min(k, scale):
+            combined_loss = torch.cat([setting.loss["reprojection"](
+                outputs[("warp_color", f, scale)], s.target) for f in self.opt.frame_ids[1:]], 1)
+            if s.automask:
+                identity_loss = torch.cat([setting.loss["reprojection"](x, s.target) for x in s.sources], 1)
+                noise = inputs[("noise", scale)] if ("noise", scale) in inputs else self._noise(identity_loss.shape)
+                combined_loss = torch.cat((identity_loss + 0.00001 * noise, combined_loss), dim=1)
+            if combined_loss.shape[1] == 1:
+                return combined_loss.mean()
+            to_optimise, outputs[("automask", scale)] = torch.min(combined_loss, dim=1)
+            return to_optimise.mean()
+        return self._scalar_tail(s, setting, mean_min, None)

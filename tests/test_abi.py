@@ -53,23 +53,48 @@ def test_prototypes_parsed_from_the_header(name, restype, argtypes):
     assert _lib.signatures()[name] == (restype, argtypes)
 
 
+def entry_point_calls(tree, sigs):
+    """{call node: [entry points it may reach]} for every call without *args of an attribute named like an entry point
+    (api.mdx_x(...), lib().mdx_x(...)), or of a local name that the same function binds to a conditional expression whose two
+    arms are such attributes (fn = api.mdx_x_nhwc_fwd if cl else api.mdx_x_fwd; fn(...): the latest binding above the call)."""
+    def entry(node):
+        return node.attr if isinstance(node, ast.Attribute) and node.attr in sigs else None
+
+    def calls(scope):
+        return [n for n in ast.walk(scope) if isinstance(n, ast.Call) and not any(isinstance(a, ast.Starred) for a in n.args)]
+    found = {node: [entry(node.func)] for node in calls(tree) if entry(node.func)}
+    for scope in ast.walk(tree):
+        if not isinstance(scope, ast.FunctionDef):
+            continue
+        bound = [(n.lineno, n.targets[0].id, [entry(n.value.body), entry(n.value.orelse)]) for n in ast.walk(scope)
+                 if isinstance(n, ast.Assign) and len(n.targets) == 1 and isinstance(n.targets[0], ast.Name)
+                 and isinstance(n.value, ast.IfExp) and entry(n.value.body) and entry(n.value.orelse)]
+        for node in calls(scope):
+            above = [names for line, name, names in sorted(bound)
+                     if isinstance(node.func, ast.Name) and name == node.func.id and line < node.lineno]
+            if above:
+                found[node] = above[-1]
+    return found
+
+
 def test_call_sites_pass_the_prototypes_argument_count():
     """Every call of an attribute named like an entry point (api.mdx_x(...), lib().mdx_x(...)) without *args, in the package,
-    tools/ and tests/, passes exactly the prototype's number of arguments: GPU-only code is checked here, on the CPU."""
+    tools/ and tests/, passes exactly the prototype's number of arguments: GPU-only code is checked here, on the CPU.  A call
+    dispatched on the layout through a local name is checked against both entry points it may reach."""
     sigs = _lib.signatures()
     files = (glob.glob(os.path.join(ROOT, PKG, "**", "*.py"), recursive=True) + glob.glob(os.path.join(ROOT, "tools", "*.py"))
              + glob.glob(os.path.join(ROOT, "tests", "*.py")))
-    calls, bad = 0, []
+    calls, dispatched, bad = 0, 0, []
     for f in files:
         with open(f) as fh:
             tree = ast.parse(fh.read(), f)
-        for node in ast.walk(tree):
-            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in sigs
-                    and not any(isinstance(a, ast.Starred) for a in node.args)):
-                calls += 1
-                if len(node.args) + len(node.keywords) != len(sigs[node.func.attr][1]):
-                    bad.append("%s:%d %s" % (os.path.relpath(f, ROOT), node.lineno, node.func.attr))
-    assert calls >= 100 and not bad, (calls, bad)
+        for node, names in entry_point_calls(tree, sigs).items():
+            calls += 1
+            dispatched += len(names) == 2
+            for name in names:
+                if len(node.args) + len(node.keywords) != len(sigs[name][1]):
+                    bad.append("%s:%d %s" % (os.path.relpath(f, ROOT), node.lineno, name))
+    assert calls >= 100 and dispatched >= 4 and not bad, (calls, dispatched, bad)
 
 
 def test_api_checks_argument_count_type_and_status():

@@ -333,3 +333,16 @@ def test_grad_sync_gather_waits_for_the_stream_backward_runs_on(monkeypatch):
     sync._issue(1)
     assert issued == [(0, ["main", "pose", "side"]), (1, ["main", "pose", "side"])], issued
     assert main.waited == pose.waited == side.waited == []     # the backward streams never wait (for each other or the gather)
+
+
+@pytest.mark.parametrize("nbytes", [0, 1, 15, 16, 17, 3 * (1 << 20) + 5])
+def test_workspace_holds_the_bytes_asked_on_a_16_byte_base(nbytes):
+    """mdx._lib.workspace, the one scratch-buffer form of the kernel layer: at least the bytes asked, never empty (a launch is
+    handed its pointer), base aligned to the 16-byte units the training kernel addresses it in, and no more than one unit
+    beyond what was asked."""
+    from mdx import _lib
+    ws = _lib.workspace(nbytes, torch.device("cpu"))
+    size = ws.numel() * ws.element_size()
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.device.type == "cpu"
+    assert size >= max(nbytes, 1) and size % 16 == 0 and size <= nbytes + 16
+    assert ws.data_ptr() % 16 == 0

@@ -59,7 +59,32 @@ def main():
     idx = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
     src = _lib.make_sources(srcs)
     what = a.what.split(",")
-    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+
+    def timeit(fn):
+        """us per call: 3 warm-up calls, then a.reps calls between two events"""
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return 1e3 * e0.elapsed_time(e1) / a.reps
+
+    def kernel_us(fn):
+        """(mean, min) us of the fused kernel alone, by the events the *_timed hook records around it: fn(hook), a.reps times"""
+        hooks = [_lib.Timing(api.mdx_event_create(), api.mdx_event_create()) for _ in range(a.reps)]
+        for hk in hooks:
+            fn(hk)
+        torch.cuda.synchronize()
+        us = []
+        for hk in hooks:
+            v = C.c_float()
+            api.mdx_event_elapsed_us(hk.start, hk.stop, C.byref(v))
+            us.append(v.value)
+        return sum(us) / len(us), min(us)
+
     all_disps = []
     for s in range(4):
         h, w = H >> s, W >> s
@@ -73,48 +98,39 @@ def main():
         color_s = torch.nn.functional.avg_pool2d(tgt, 2 ** s) if s else tgt
         d = _lib.make_desc(B, H, W, h, w, S, True, 0.1, 100.0)
         nws = api.mdx_photometric_workspace_bytes(C.byref(d))
-        ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace(nws, dev)
         gdisp, gP = torch.empty_like(disp), torch.empty(S, B, 3, 4, device=dev)
         loss = torch.empty(1, device=dev)
         nsw = api.mdx_smooth_workspace_bytes(B, h, w)
-        sws = torch.empty(nsw // 8 + 1, dtype=torch.float64, device=dev)
+        sws = _lib.workspace(nsw, dev)
 
         def fwd():
             api.mdx_photometric_fwd(
                 C.byref(d), _lib.ptr(disp), _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), _lib.ptr(P),
                 _lib.ptr(ident), _lib.ptr(noise), _lib.ptr(idx, torch.uint8), None, None, None,
                 _lib.ptr(warp) if a.save_warp in (1, 3) else None, None, _lib.ptr(coef) if a.save_warp >= 2 else None,
-                _lib.ptr(ws, torch.float64), nws, _lib.stream())
+                _lib.ptr(ws, torch.uint8), nws, _lib.stream())
 
         def bwd():
             api.mdx_photometric_bwd(
                 C.byref(d), _lib.ptr(disp), _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), _lib.ptr(P),
                 _lib.ptr(idx, torch.uint8), _lib.ptr(warp) if a.save_warp in (1, 3) else None,
                 _lib.ptr(coef) if a.save_warp >= 2 else None, 1e-6, None, _lib.ptr(gdisp), _lib.ptr(gP),
-                _lib.ptr(ws, torch.float64), nws, _lib.stream())
+                _lib.ptr(ws, torch.uint8), nws, _lib.stream())
 
         def ident_fn():
             F.identity_loss(tgt, srcs)
 
         def smooth():
             api.mdx_smooth_loss(B, h, w, _lib.ptr(disp), _lib.ptr(color_s), 1, _lib.ptr(loss), _lib.ptr(gdisp),
-                                _lib.ptr(sws, torch.float64), nsw, _lib.stream())
+                                _lib.ptr(sws, torch.uint8), nsw, _lib.stream())
         fwd()
         fns = {"fwd": fwd, "bwd": bwd, "ident": ident_fn, "smooth": smooth}
         out = []
         for name in what:
             if name in ("train", "pre") or (name == "ident" and s):
                 continue
-            fn = fns[name]
-            for _ in range(3):
-                fn()
-            e0, e1 = ev(), ev()
-            e0.record()
-            for _ in range(a.reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            out.append("%s %.1f us" % (name, 1e3 * e0.elapsed_time(e1) / a.reps))
+            out.append("%s %.1f us" % (name, timeit(fns[name])))
         print("scale %d: %s  (masked %.1f%%)" % (s, ", ".join(out), 100.0 * float((idx < S).float().mean())), flush=True)
 
     if "pre" in what:
@@ -123,17 +139,6 @@ def main():
         disps = [x.clone().requires_grad_(True) for x in all_disps[:nsc]]
         noises = [torch.randn(B, S, H, W, generator=g).to(dev) for _ in range(nsc)]
         st = F.noise_state(dev, seed=1)
-
-        def timeit(fn):
-            for _ in range(3):
-                fn()
-            e0, e1 = ev(), ev()
-            e0.record()
-            for _ in range(a.reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            return 1e3 * e0.elapsed_time(e1) / a.reps
         t_drawn = timeit(lambda: F.photometric_prologue(tgt, srcs, nsc, rng=st))
         t_inj = timeit(lambda: F.photometric_prologue(tgt, srcs, nsc, noises=noises))
         t_randn = timeit(lambda: torch.randn((nsc, B, S, H, W), device=dev))
@@ -146,7 +151,7 @@ def main():
         gdisps = [torch.empty_like(x) for x in disps]
         gPs = torch.empty(nsc, S, B, 3, 4, device=dev)
         nws = api.mdx_photometric_train_workspace_bytes(C.byref(td))
-        ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
+        ws = _lib.workspace(nws, dev)
         pd, pP = _lib.ptr_array([x.detach() for x in disps]), _lib.ptr_array([P] * nsc)
         pi, pg, pb = _lib.ptr_array(idxs, torch.uint8), _lib.ptr_array(gdisps), _lib.ptr_array(pre["bidfi"])
 
@@ -154,26 +159,15 @@ def main():
             api.mdx_photometric_train_pre(
                 C.byref(td), pd, _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), pP, _lib.ptr(pre["tstat"]), pb, None, pi,
                 _lib.ptr(sums), pg if grads else None, _lib.ptr(gPs) if grads else None, None, None,
-                _lib.ptr(ws, torch.float64), nws, _lib.stream(), C.byref(hook) if hook is not None else None)
+                _lib.ptr(ws, torch.uint8), nws, _lib.stream(), C.byref(hook) if hook is not None else None)
 
-        def kernel_us(grads):
-            hooks = [_lib.Timing(api.mdx_event_create(), api.mdx_event_create()) for _ in range(a.reps)]
-            for hk in hooks:
-                train_pre(grads, hk)
-            torch.cuda.synchronize()
-            us = []
-            for hk in hooks:
-                v = C.c_float()
-                api.mdx_event_elapsed_us(hk.start, hk.stop, C.byref(v))
-                us.append(v.value)
-            return sum(us) / len(us)
         t_call = timeit(lambda: train_pre(True))
         t_eval = timeit(lambda: train_pre(False))
-        tsum, esum = {"train": (kernel_us(True), a.reps)}, {"eval": (kernel_us(False), a.reps)}
+        k_train, k_eval = kernel_us(lambda hk: train_pre(True, hk))[0], kernel_us(lambda hk: train_pre(False, hk))[0]
         print("prologue: drawn noise %.1f us, injected noise %.1f us (torch.randn of the %d x [B,S,H,W] maps alone: %.1f us)"
               % (t_drawn, t_inj, nsc, t_randn))
         print("train_pre (%d scales): whole call %.1f us, fused kernel %.1f us; forward-only form: call %.1f us, kernel %.1f us"
-              % (nsc, t_call, tsum["train"][0], t_eval, esum["eval"][0]), flush=True)
+              % (nsc, t_call, k_train, t_eval, k_eval), flush=True)
 
     if "train" in what:
         nsc = a.nscales
@@ -185,36 +179,20 @@ def main():
         gdisps = [torch.empty_like(x) for x in disps]
         gPs = torch.empty(nsc, S, B, 3, 4, device=dev)
         nws = api.mdx_photometric_train_workspace_bytes(C.byref(td))
-        ws = torch.empty(nws // 16 + 1, 2, dtype=torch.float64, device=dev)
+        ws = _lib.workspace(nws, dev)
         pd, pP, pn = _lib.ptr_array(disps), _lib.ptr_array([P] * nsc), _lib.ptr_array(noises)
         pi, pg = _lib.ptr_array(idxs, torch.uint8), _lib.ptr_array(gdisps)
 
         def train(hook=None):
             api.mdx_photometric_train(
                 C.byref(td), pd, _lib.ptr(tgt), C.byref(src), _lib.ptr(invK), pP, _lib.ptr(ident), pn, pi,
-                _lib.ptr(sums), pg, _lib.ptr(gPs), None, None, _lib.ptr(ws, torch.float64), nws,
+                _lib.ptr(sums), pg, _lib.ptr(gPs), None, None, _lib.ptr(ws, torch.uint8), nws,
                 _lib.stream(), C.byref(hook) if hook is not None else None)
-        for _ in range(3):
-            train()
-        e0, e1 = ev(), ev()
-        e0.record()
-        for _ in range(a.reps):
-            train()
-        e1.record()
-        e1.synchronize()
-        hooks = [_lib.Timing(api.mdx_event_create(), api.mdx_event_create()) for _ in range(a.reps)]
-        for hk in hooks:
-            train(hk)
-        torch.cuda.synchronize()
-        us = []
-        for hk in hooks:
-            v = C.c_float()
-            api.mdx_event_elapsed_us(hk.start, hk.stop, C.byref(v))
-            us.append(v.value)
+        t_call = timeit(train)
+        k_mean, k_min = kernel_us(train)
         if os.environ.get("MDX_TRAIN_STAMPS"):   # diagnostic library build: per-item phase clocks at the workspace's end
             items = int(os.environ["MDX_TRAIN_STAMPS"])
             torch.cuda.synchronize()
-            st = ws.view(torch.int64).reshape(-1)[-(items * 8 + 2):-2].reshape(items, 8).cpu().double()
             # the tensor is a little larger than the workspace: find the block by its step-count column
             raw = ws.view(torch.int64).reshape(-1).cpu()
             nb = nws // 8
@@ -248,7 +226,7 @@ def main():
                 t0.median(), t0.max(), st[:, 4].min(), st[:, 4].max()))
         masked = [100.0 * float((i < S).float().mean()) for i in idxs]
         print("train (%d scales, rows/chunk %d): whole call %.1f us, fused kernel %.1f us (min %.1f)  masked %s"
-              % (nsc, a.rows, 1e3 * e0.elapsed_time(e1) / a.reps, sum(us) / len(us), min(us),
+              % (nsc, a.rows, t_call, k_mean, k_min,
                  " ".join("%.1f%%" % m for m in masked)), flush=True)
 
 
