@@ -3,8 +3,16 @@
 Same class from the outside (reference model_tool/loader.py:93-97 builds torch.optim.Adam): parameter groups, `state_dict()` /
 `load_state_dict()` (per-parameter "step", "exp_avg", "exp_avg_sq"), capturable learning-rate tensors (model_train.graphed_step).
 What the kernel does not cover -- weight decay, amsgrad, maximize, a closure, a GradScaler's grad_scale / found_inf, parameters that
-are not dense float32 GPU tensors -- goes through torch's own step."""
+are not dense float32 GPU tensors -- goes through torch's own step.
+
+The step guard (off by default): `Adam(params, lr, max_grad_norm=1.0, skip_nonfinite=True)` clips by the global L2 norm of every
+gradient the step consumes and / or leaves parameters, moments and step counts untouched when that norm is not finite.  On the native
+path the decision is taken on the device (three launches, capturable, no host synchronisation, deterministic; `.grad` is never
+written); `guard_stats()` is the only call that synchronises.  Where the step goes through torch's own functions -- CPU parameters,
+anything `_native_ok` rejects -- the guard does too: a float64 norm and a HOST-side skip (so that path cannot be captured), then
+`torch.nn.utils.clip_grad_norm_`, which scales `.grad` in place.  The guard's record is not part of `state_dict()`."""
 import ctypes as C
+import struct
 
 import torch
 
@@ -17,10 +25,24 @@ class _Table(C.Structure):
 
 
 class Adam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, **kw):
+    native = True          # False: every step goes through torch's own (the guard with it)
+
+    def __init__(self, params, lr=1e-3, max_grad_norm=None, skip_nonfinite=False, **kw):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("max_grad_norm must be positive or None, got %r" % (max_grad_norm,))
         kw.setdefault("fused", True)
         super().__init__(params, lr, **kw)
         self._plans = {}
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard = None               # the guarded step's plan: one table over every group, partials, launches
+        self._record = None              # the device record (include/mdx.h: mdx_adam_guard_finish)
+        self._host_stats = dict(total_norm=0.0, coef=1.0, skipped=False, steps=0, skipped_steps=0)   # torch-path guard
+        self._last_native = True
+
+    @property
+    def guarded(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
 
     # -- what one launch needs, built once per parameter group -------------------------------------------------------------
     def _plan(self, gi, params, exp_avgs, exp_avg_sqs, steps):
@@ -28,25 +50,54 @@ class Adam(torch.optim.Adam):
         plan = self._plans.get(gi)
         if plan is not None and plan["key"] == key:
             return plan
+        plan = dict(key=key, table=self._table(params, exp_avgs, exp_avg_sqs, steps), launches=self._launches(params, 0))
+        self._plans[gi] = plan
+        return plan
+
+    @staticmethod
+    def _table(params, exp_avgs, exp_avg_sqs, steps):
         assert C.sizeof(_Table) == api.mdx_adam_table_entry_bytes()
-        dev = params[0].device
-        n = len(params)
-        host = (_Table * n)()
+        host = (_Table * len(params))()
         for i, (p, m, v, s) in enumerate(zip(params, exp_avgs, exp_avg_sqs, steps)):
             host[i] = _Table(p.data_ptr(), m.data_ptr(), v.data_ptr(), s.data_ptr(), p.numel())
         raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone()
-        table = raw.to(dev)
+        return raw.to(params[0].device)
+
+    @staticmethod
+    def _launches(params, base):
+        """[(first table entry, count, block map, blocks)] covering `params`, whose table entries start at `base`."""
         chunk, per = api.mdx_adam_chunk(), api.mdx_adam_max_tensors()
         launches = []
-        for first in range(0, n, per):
-            count = min(per, n - first)
+        for first in range(0, len(params), per):
+            count = min(per, len(params) - first)
             bm = []
             for t in range(count):
                 bm += [(t, c) for c in range((params[first + t].numel() + chunk - 1) // chunk)]
-            blockmap = torch.tensor(bm, dtype=torch.int32).to(dev)
-            launches.append((first, count, blockmap, len(bm)))
-        plan = dict(key=key, table=table, launches=launches)
-        self._plans[gi] = plan
+            blockmap = torch.tensor(bm, dtype=torch.int32).to(params[0].device)
+            launches.append((base + first, count, blockmap, len(bm)))
+        return launches
+
+    def _guard_plan(self, todo):
+        """The guarded step's plan: ONE table over the tensors of every group (the norm is global), each group's launches with
+        their slice of the partials buffer, the record.  Built in the first (eager, warm-up) step, never inside a capture."""
+        key = tuple(t.data_ptr() for _, _, params, _, exp_avgs, exp_avg_sqs, steps in todo
+                    for ts in (params, exp_avgs, exp_avg_sqs, steps) for t in ts)
+        plan = self._guard
+        if plan is not None and plan["key"] == key:
+            return plan
+        dev = todo[0][2][0].device
+        cat = [sum((list(item[k]) for item in todo), []) for k in (2, 4, 5, 6)]
+        launches, base, slot = [], 0, 0
+        for ti, (_, _, params, _, _, _, _) in enumerate(todo):
+            for first, count, blockmap, nblocks in self._launches(params, base):
+                launches.append((ti, first, first - base, count, blockmap, nblocks, slot))
+                slot += nblocks
+            base += len(params)
+        if self._record is None or self._record.device != dev:
+            self._record = torch.zeros(api.mdx_adam_guard_record_bytes() // 8, dtype=torch.int64, device=dev)
+        partials = torch.empty(api.mdx_adam_guard_partials_bytes(slot) // 8, dtype=torch.float64, device=dev)
+        plan = dict(key=key, table=self._table(*cat), launches=launches, partials=partials, ntensors=base, nblocks=slot)
+        self._guard = plan
         return plan
 
     @staticmethod
@@ -54,7 +105,7 @@ class Adam(torch.optim.Adam):
         return a.stride() == b.stride() and a.shape == b.shape
 
     def _native_ok(self, group, params, grads, exp_avgs, exp_avg_sqs, steps):
-        if group["weight_decay"] != 0 or group["amsgrad"] or group["maximize"] or group.get("differentiable"):
+        if not self.native or group["weight_decay"] != 0 or group["amsgrad"] or group["maximize"] or group.get("differentiable"):
             return False
         if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
             return False
@@ -70,7 +121,12 @@ class Adam(torch.optim.Adam):
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
-            return super().step(closure)
+            if not self.guarded:
+                return super().step(closure)
+            with torch.enable_grad():
+                loss = closure()
+            self._torch_guarded_step()
+            return loss
         todo = []
         for gi, group in enumerate(self.param_groups):
             params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps = [], [], [], [], [], []
@@ -78,8 +134,12 @@ class Adam(torch.optim.Adam):
             if not params:
                 continue
             if not self._native_ok(group, params, grads, exp_avgs, exp_avg_sqs, steps):
-                return super().step()
+                return self._torch_guarded_step() if self.guarded else super().step()
             todo.append((gi, group, params, grads, exp_avgs, exp_avg_sqs, steps))
+        if self.guarded and todo:
+            if len({item[2][0].device for item in todo}) > 1:        # one table, one record: one device
+                return self._torch_guarded_step()
+            return self._native_guarded_step(todo)
         for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps in todo:
             if params[0].device.index != torch.cuda.current_device():
                 raise _lib.MdxError("mdx.optim.Adam: parameters live on %s but the current device is cuda:%d"
@@ -96,3 +156,79 @@ class Adam(torch.optim.Adam):
                 api.mdx_adam_step(plan["table"].data_ptr(), first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr,
                                   0.0 if lr_ptr is not None else float(lr), beta1, beta2, group["eps"], stream())
         return None
+
+    # -- the guarded step ---------------------------------------------------------------------------------------------------
+    def _native_guarded_step(self, todo):
+        """Sum of squares (one launch per <= mdx_adam_max_tensors() tensors), finish (norm, coefficient, skip flag, totals, step
+        counts), guarded Adam: include/mdx.h.  Nothing here looks at a value on the host."""
+        dev = todo[0][2][0].device
+        if dev.index != torch.cuda.current_device():
+            raise _lib.MdxError("mdx.optim.Adam: parameters live on %s but the current device is cuda:%d"
+                                % (dev, torch.cuda.current_device()))
+        plan = self._guard_plan(todo)
+        table, partials, record = plan["table"].data_ptr(), plan["partials"].data_ptr(), self._record.data_ptr()
+        garrs = []
+        for ti, first, local, count, blockmap, nblocks, slot in plan["launches"]:
+            garr = (C.c_void_p * count)(*[g.data_ptr() for g in todo[ti][3][local:local + count]])
+            garrs.append(garr)
+            api.mdx_adam_grad_sumsq(table, first, count, garr, blockmap.data_ptr(), nblocks, partials + 8 * slot, stream())
+        api.mdx_adam_guard_finish(table, plan["ntensors"], partials, plan["nblocks"], self.max_grad_norm or 0.0,
+                                  int(self.skip_nonfinite), record, stream())
+        for garr, (ti, first, local, count, blockmap, nblocks, slot) in zip(garrs, plan["launches"]):
+            group = todo[ti][1]
+            lr = group["lr"]
+            lr_ptr = lr.data_ptr() if torch.is_tensor(lr) else None
+            if torch.is_tensor(lr) and not (lr.is_cuda and lr.dtype == torch.float32):
+                lr, lr_ptr = float(lr), None
+            beta1, beta2 = group["betas"]
+            api.mdx_adam_step_guarded(table, first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr,
+                                      0.0 if lr_ptr is not None else float(lr), beta1, beta2, group["eps"], record, stream())
+        self._last_native = True
+        return None
+
+    def _torch_guarded_step(self):
+        """The guard around torch's own step: the norm in float64 (a large finite gradient stays finite), the skip decided on the
+        host, then clip_grad_norm_ -- which scales .grad in place -- and torch's Adam."""
+        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not grads:
+            return super().step()
+        norms = [torch.linalg.vector_norm(g.detach(), 2.0, dtype=torch.float64) for g in grads]
+        norm = torch.linalg.vector_norm(torch.stack([n.to(norms[0].device) for n in norms])).float().cpu()
+        coef = torch.ones(())
+        if self.max_grad_norm is not None:
+            coef = torch.clamp(torch.tensor(self.max_grad_norm) / (norm + 1e-6), max=1.0)
+        skipped = self.skip_nonfinite and not bool(torch.isfinite(norm))
+        st = self._host_stats
+        st.update(total_norm=float(norm), coef=float(coef), skipped=skipped, steps=st["steps"] + 1,
+                  skipped_steps=st["skipped_steps"] + int(skipped))
+        self._last_native = False
+        if skipped:
+            return None
+        if self.max_grad_norm is not None:
+            torch.nn.utils.clip_grad_norm_([p for g in self.param_groups for p in g["params"] if p.grad is not None],
+                                           self.max_grad_norm)
+        return super().step()
+
+    def guard_stats(self):
+        """{total_norm, coef, skipped: of the last guarded step; steps, skipped_steps: running totals}.  Reads the device record:
+        the one place of the guard that synchronises."""
+        out = dict(self._host_stats)
+        if self._record is not None:
+            norm, coef, skipped, _, steps, skipped_steps = struct.unpack("<ffiiqq", self._record.cpu().numpy().tobytes())
+            if self._last_native:
+                out.update(total_norm=norm, coef=coef, skipped=bool(skipped))
+            out["steps"] += steps
+            out["skipped_steps"] += skipped_steps
+        return out
+
+    def guard_snapshot(self):
+        """The guard's record and totals, for a caller that undoes steps (model_train.graphed_step's warm-up)."""
+        return (None if self._record is None else self._record.clone(), dict(self._host_stats), self._last_native)
+
+    def guard_restore(self, snapshot):
+        record, self._host_stats, self._last_native = snapshot[0], dict(snapshot[1]), snapshot[2]
+        if self._record is not None:
+            if record is not None:
+                self._record.copy_(record)
+            else:
+                self._record.zero_()             # no guarded step had run

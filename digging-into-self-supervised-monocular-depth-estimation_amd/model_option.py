@@ -59,6 +59,12 @@ def options(argv=None):
                    help="restart after this many finished epochs from ./model_save/<save>/ (weights <key><N>.pt + state<N>.pt)")
     p.add_argument("--native_adam", type=int, default=1,
                    help="GPU: torch.optim.Adam(fused=True) with its step as ONE launch (mdx/optim.py, csrc/adam.hip); 0: torch's own step")
+    p.add_argument("--clip_grad_norm", type=float, default=0.0,
+                   help="clip the gradients to this global L2 norm inside the optimiser step, decided on the device (mdx/optim.py: "
+                        "max_grad_norm; three launches, capturable); 0: off")
+    p.add_argument("--skip_nonfinite", type=int, default=0,
+                   help="1: a step whose global gradient norm is not finite changes no weight, moment or step count (decided on the "
+                        "device; counted, printed after each epoch)")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

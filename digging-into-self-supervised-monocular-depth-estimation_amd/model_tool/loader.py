@@ -151,9 +151,18 @@ class setting(object):
 
     # reference: loader.py:106-109
     def set_optim(self):
+        # the step guard (--clip_grad_norm, --skip_nonfinite; both off by default): mdx.optim.Adam on every device, whose guard takes
+        # torch's own functions where the native step does not run
+        clip, skip = float(_opt(self.opt, "clip_grad_norm", 0.0) or 0.0), bool(_opt(self.opt, "skip_nonfinite", False))
+        guard = dict(max_grad_norm=clip if clip > 0 else None, skip_nonfinite=skip)
         if str(self.device).startswith("cuda") and _opt(self.opt, "native_adam", True):
             from mdx.optim import Adam             # torch.optim.Adam(fused=True) with its step as one launch (csrc/adam.hip)
-            self.optim["optimizer"] = Adam(self.parameters, float(self.opt.learning_rate))
+            self.optim["optimizer"] = Adam(self.parameters, float(self.opt.learning_rate), **guard)
+        elif clip > 0 or skip:
+            from mdx.optim import Adam
+            fused = str(self.device).startswith("cuda")
+            self.optim["optimizer"] = Adam(self.parameters, float(self.opt.learning_rate), fused=fused, **guard)
+            self.optim["optimizer"].native = False          # --native_adam 0 / CPU: torch's step, guarded
         else:
             fused = str(self.device).startswith("cuda")
             self.optim["optimizer"] = torch.optim.Adam(self.parameters, float(self.opt.learning_rate), fused=fused)

@@ -97,7 +97,11 @@ class graphed_step(object):
     The warm-up steps capture needs (MIOpen picks its kernels, the allocator settles, RCCL opens its communicator) are
     side-effect free: weights, batch-norm statistics, Adam moments, step counters and the offset of the in-kernel noise
     generator are put back afterwards, so the first replay is step 1 of the run -- graph on and graph off follow the same
-    trajectory and draw the same noise."""
+    trajectory and draw the same noise.
+
+    The step guard (--clip_grad_norm, --skip_nonfinite) is part of optimizer.step(): it runs after the gradient exchange, on the
+    exchanged gradients, so every rank sees the same bits and takes the same decision; in the split form it is part of graph B.
+    Its totals are put back after the warm-up with the moments and step counters."""
 
     def __init__(self, tr, example, warmup=3):
         self.tr = tr
@@ -129,6 +133,7 @@ class graphed_step(object):
         saved_rng = rng.tensor.clone() if rng is not None else None
         had_state = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                      for p, st in opt.state.items()}
+        saved_guard = opt.guard_snapshot() if getattr(opt, "guarded", False) else None     # the step guard's totals (mdx/optim.py)
         # ONE side stream for the warm-up and the capture: the gradient-accumulation nodes autograd creates during
         # the captured forward then live on the stream that produces their gradients
         self.stream = torch.cuda.Stream(dev)
@@ -149,6 +154,8 @@ class graphed_step(object):
                                 v.zero_()          # Adam's initial state: zero moments, step 0
                 if rng is not None:
                     rng.tensor.copy_(saved_rng)
+                if saved_guard is not None:
+                    opt.guard_restore(saved_guard)
             for m, n in zip(self.bns, saved_bn):
                 m._pending_batches = n
         torch.cuda.current_stream(dev).wait_stream(self.stream)
@@ -428,6 +435,11 @@ class trainer(object):
                 epoch_valid[key].append(mean_valid[key])
             if self.rank == 0:
                 self.control.print(epoch, mean_train, mean_valid)
+                optimizer = self.setting.optim["optimizer"]
+                if getattr(optimizer, "guarded", False):
+                    g = optimizer.guard_stats()
+                    print("step guard: %d steps, %d skipped, last gradient norm %g" % (g["steps"], g["skipped_steps"], g["total_norm"]),
+                          flush=True)
             self.control.save(epoch, epoch_train, epoch_valid, self.setting, compute=self.compute)
 
 

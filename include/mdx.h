@@ -242,6 +242,34 @@ size_t mdx_adam_table_entry_bytes(void);
 int mdx_adam_step(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
                   const float *lr_ptr, double lr, double beta1, double beta2, double eps, void *stream);
 
+/* The guarded step: clip by the global gradient norm and / or skip a step whose norm is not finite, decided on the device (a
+ * captured loop cannot branch on the host).  Three launches instead of torch._foreach_add_(steps, 1) + mdx_adam_step, ordered by
+ * the stream alone -- no atomics, no block waits for another:
+ *   mdx_adam_grad_sumsq    table / first / count / grads / blockmap / nblocks as for mdx_adam_step (only numel is read); block b
+ *                          writes the sum of g^2 over its chunk, squared and added in double, to partials[b] (DEVICE, nblocks
+ *                          doubles, mdx_adam_guard_partials_bytes(nblocks)).  Several calls (more than mdx_adam_max_tensors()
+ *                          tensors, several parameter groups) take disjoint slices of one partials buffer.
+ *   mdx_adam_guard_finish  one block: adds partials[0 .. npartials - 1] in a fixed order and writes the DEVICE record
+ *                          (mdx_adam_guard_record_bytes(), 8-byte aligned, zeroed once by the caller):
+ *                            { float total_norm = (float)sqrt(sum);  float coef;  int32 skipped;  int32 reserved;
+ *                              int64 steps;  int64 skipped_steps }
+ *                          coef = min(1, max_grad_norm / (total_norm + 1e-6)) in float32, or exactly 1 when max_grad_norm <= 0
+ *                          (no clipping); skipped = skip_nonfinite && !isfinite(total_norm).  steps += 1, skipped_steps +=
+ *                          skipped.  Unless skipped it adds 1 to the step count of table entries 0 .. ntensors - 1 (step is the
+ *                          count BEFORE this step here: the caller does not increment it).
+ *   mdx_adam_step_guarded  mdx_adam_step reading the record: returns at once when skipped (parameters, moments and step counts keep
+ *                          their bits), otherwise consumes g * coef -- one float32 multiply, rounded before Adam's own arithmetic;
+ *                          coef == 1 gives mdx_adam_step's bits.  The gradients are never written.
+ * A NaN max_grad_norm is MDX_ERR_BAD_SHAPE. */
+size_t mdx_adam_guard_record_bytes(void);
+size_t mdx_adam_guard_partials_bytes(int nblocks);
+int mdx_adam_grad_sumsq(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
+                        double *partials, void *stream);
+int mdx_adam_guard_finish(const void *table, int ntensors, const double *partials, int npartials, double max_grad_norm,
+                          int skip_nonfinite, void *record, void *stream);
+int mdx_adam_step_guarded(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
+                          const float *lr_ptr, double lr, double beta1, double beta2, double eps, const void *record, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fine-grained ops behind the reference's model_layer / model_loss API (each differentiable)
  * ---------------------------------------------------------------------------------------- */
