@@ -22,7 +22,6 @@ namespace nhwc {
 constexpr int DH_NB = 256;
 constexpr int DH_N = 4;          // channels per thread, float32 AND bfloat16 (8 bfloat16 per thread doubled the accumulators: 192 registers,
                                  // two waves per SIMD, the backward pass twice as slow as the float32 one)
-enum { MDX_F32 = 0, MDX_BF16 = 1 };   // the dtype codes of include/mdx.h
 
 template <typename T, int N>
 __device__ __forceinline__ void load_weights(const float *__restrict__ wt, long wsc, long wsy, long wsx, int c0, float (&wr)[9][N])
@@ -245,7 +244,7 @@ using namespace mdx::nhwc;
 
 static int head_args_ok(int B, int C, int h, int w, int dtype)
 {
-    if (dtype != MDX_F32 && dtype != MDX_BF16) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || C > 1024) return MDX_ERR_BAD_SHAPE;
     if ((long long)B * (h + 2) * (w + 2) >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
     return MDX_OK;
@@ -267,12 +266,11 @@ MDX_EXPORT int mdx_disp_head_nhwc_fwd(const void *x, const float *weight, int64_
     if (!aligned(x, 16)) return MDX_ERR_MISALIGNED;
     HeadGeom g;
     if (!head_geom(B, h, w, C, dtype, &g)) return MDX_ERR_BAD_SHAPE;
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((disp_head_fwd_kernel<float>), g.grid, dim3(DH_NB), 0, (hipStream_t)stream, (const float *)x, weight,
-                           (long)w_stride_c, (long)w_stride_ky, (long)w_stride_kx, bias, h + 2, w + 2, C, g.LP, g.R, disp);
-    else
-        hipLaunchKernelGGL((disp_head_fwd_kernel<bf16>), g.grid, dim3(DH_NB), 0, (hipStream_t)stream, (const bf16 *)x, weight,
-                           (long)w_stride_c, (long)w_stride_ky, (long)w_stride_kx, bias, h + 2, w + 2, C, g.LP, g.R, disp);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((disp_head_fwd_kernel<T>), g.grid, dim3(DH_NB), 0, (hipStream_t)stream, (const T *)x, weight, (long)w_stride_c,
+                           (long)w_stride_ky, (long)w_stride_kx, bias, h + 2, w + 2, C, g.LP, g.R, disp);
+    });
     return check_launch();
 }
 
@@ -290,12 +288,11 @@ MDX_EXPORT int mdx_disp_head_nhwc_bwd(const void *x, const float *weight, int64_
     float *part = (float *)workspace;
     const size_t shmem = ((size_t)(DH_NB / 64) * 9 * C + DH_NB / 64) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((disp_head_bwd_kernel<float, 4>), g.grid, dim3(DH_NB), shmem, st, (const float *)x, weight, (long)w_stride_c,
-                           (long)w_stride_ky, (long)w_stride_kx, gdisp, disp, h + 2, w + 2, C, g.LP, g.R, (float *)gx, part);
-    else
-        hipLaunchKernelGGL((disp_head_bwd_kernel<bf16, 4>), g.grid, dim3(DH_NB), shmem, st, (const bf16 *)x, weight, (long)w_stride_c,
-                           (long)w_stride_ky, (long)w_stride_kx, gdisp, disp, h + 2, w + 2, C, g.LP, g.R, (bf16 *)gx, part);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((disp_head_bwd_kernel<T, 4>), g.grid, dim3(DH_NB), shmem, st, (const T *)x, weight, (long)w_stride_c,
+                           (long)w_stride_ky, (long)w_stride_kx, gdisp, disp, h + 2, w + 2, C, g.LP, g.R, (T *)gx, part);
+    });
     const int nblk = (int)(g.grid.x * g.grid.y * g.grid.z), cols = 9 * C + 1;
     hipLaunchKernelGGL(disp_head_finish_kernel, dim3((cols + DF_C - 1) / DF_C), dim3(DF_C * DF_S), 0, st, part, nblk, C,
                        (long)w_stride_c, (long)w_stride_ky, (long)w_stride_kx, gweight, gbias);

@@ -11,27 +11,11 @@
 //                  index of the first maximum (ATen's strict-> scan), backward gathers from the <= 4 windows that
 //                  contain an input position.
 // float32 and bfloat16 (networks under autocast) storage, arithmetic in float32.  Thread <-> x: rows coalesce.
-#include "mdx_common.hpp"
-#include <stdint.h>
+#include "mdx_dtype.hpp"
 
 namespace mdx {
 
-struct bf16 { uint16_t v; };
-
-__device__ __forceinline__ float to_float(float x) { return x; }
-__device__ __forceinline__ float to_float(bf16 x) { return __uint_as_float((uint32_t)x.v << 16); }
-template <typename T> __device__ __forceinline__ T from_float(float x);
-template <> __device__ __forceinline__ float from_float<float>(float x) { return x; }
-template <> __device__ __forceinline__ bf16 from_float<bf16>(float x)
-{
-    // round to nearest even, NaN stays NaN (torch's float -> bfloat16)
-    uint32_t u = __float_as_uint(x);
-    bf16 r;
-    if ((u & 0x7fffffffu) > 0x7f800000u) { r.v = (uint16_t)((u >> 16) | 0x40u); return r; }
-    u += 0x7fffu + ((u >> 16) & 1u);
-    r.v = (uint16_t)(u >> 16);
-    return r;
-}
+template <typename T> __device__ __forceinline__ T from_float(float x) { return from_float_int<T>(x); }     // the integer conversion (mdx_dtype.hpp)
 
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : __expf(x) - 1.0f; }   // ATen: exp(x) - 1
@@ -310,9 +294,6 @@ static inline dim3 grid3r(int nx, int ny, int nz) { return dim3((nx + GX - 1) / 
 
 using namespace mdx;
 
-// dtype codes of the glue entry points
-enum { MDX_F32 = 0, MDX_BF16 = 1 };
-
 MDX_EXPORT int mdx_decoder_glue_fwd(const void *raw, const void *skip, const float *bias, void *out, int B, int C1, int C2,
                                     int h, int w, int upsample, int elu, int in_dtype, int out_dtype, void *stream)
 {
@@ -322,17 +303,13 @@ MDX_EXPORT int mdx_decoder_glue_fwd(const void *raw, const void *skip, const flo
         return MDX_ERR_BAD_SHAPE;
     const dim3 grid = grid3r(w * u + 2, h * u + 2, B * (C1 + C2)), block(GX, GY);
     hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == MDX_F32 && out_dtype == MDX_F32)
-        hipLaunchKernelGGL((decoder_glue_fwd_kernel<float, float>), grid, block, 0, st, (const float *)raw,
-                           (const float *)skip, bias, (float *)out, C1, C2, h, w, upsample, elu);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_BF16)
-        hipLaunchKernelGGL((decoder_glue_fwd_kernel<bf16, bf16>), grid, block, 0, st, (const bf16 *)raw,
-                           (const bf16 *)skip, bias, (bf16 *)out, C1, C2, h, w, upsample, elu);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_F32)
-        hipLaunchKernelGGL((decoder_glue_fwd_kernel<bf16, float>), grid, block, 0, st, (const bf16 *)raw,
-                           (const bf16 *)skip, bias, (float *)out, C1, C2, h, w, upsample, elu);
-    else
-        return MDX_ERR_BAD_SHAPE;
+    const bool built = dispatch_dtype_pair(in_dtype, out_dtype, [&](auto ti, auto to) {
+        using TI = typename decltype(ti)::type;
+        using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL((decoder_glue_fwd_kernel<TI, TO>), grid, block, 0, st, (const TI *)raw, (const TI *)skip, bias, (TO *)out,
+                           C1, C2, h, w, upsample, elu);
+    });
+    if (!built) return MDX_ERR_BAD_SHAPE;
     return check_launch();
 }
 
@@ -354,23 +331,18 @@ MDX_EXPORT int mdx_decoder_glue_bwd(const void *gout, const void *raw, const flo
         return MDX_ERR_BAD_SHAPE;
     const dim3 block(GX, GY), graw_grid = grid3r(w, h, B * C1), gskip_grid = grid3r(w * u, h * u, B * (C2 > 0 ? C2 : 1));
     hipStream_t st = (hipStream_t)stream;
-#define MDX_GLUE_BWD(TI, TO)                                                                                          \
-    do {                                                                                                              \
-        if (upsample)                                                                                                 \
-            hipLaunchKernelGGL((decoder_glue_bwd_raw_kernel<TI, TO, 2>), graw_grid, block, 0, st, (const TO *)gout,   \
-                               (const TI *)raw, bias, (TI *)graw, bias_part, C1, C2, h, w, elu);                       \
-        else                                                                                                          \
-            hipLaunchKernelGGL((decoder_glue_bwd_raw_kernel<TI, TO, 1>), graw_grid, block, 0, st, (const TO *)gout,   \
-                               (const TI *)raw, bias, (TI *)graw, bias_part, C1, C2, h, w, elu);                       \
-        if (C2 > 0)                                                                                                   \
-            hipLaunchKernelGGL((decoder_glue_bwd_skip_kernel<TI, TO>), gskip_grid, block, 0, st, (const TO *)gout,    \
-                               (TI *)gskip, C1, C2, h * u, w * u);                                                     \
-    } while (0)
-    if (in_dtype == MDX_F32 && out_dtype == MDX_F32) MDX_GLUE_BWD(float, float);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_BF16) MDX_GLUE_BWD(bf16, bf16);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_F32) MDX_GLUE_BWD(bf16, float);
-    else return MDX_ERR_BAD_SHAPE;
-#undef MDX_GLUE_BWD
+    const bool built = dispatch_dtype_pair(in_dtype, out_dtype, [&](auto ti, auto to) {
+        using TI = typename decltype(ti)::type;
+        using TO = typename decltype(to)::type;
+        dispatch_flag(upsample != 0, [&](auto up) {
+            hipLaunchKernelGGL((decoder_glue_bwd_raw_kernel<TI, TO, decltype(up)::value ? 2 : 1>), graw_grid, block, 0, st,
+                               (const TO *)gout, (const TI *)raw, bias, (TI *)graw, bias_part, C1, C2, h, w, elu);
+        });
+        if (C2 > 0)
+            hipLaunchKernelGGL((decoder_glue_bwd_skip_kernel<TI, TO>), gskip_grid, block, 0, st, (const TO *)gout, (TI *)gskip, C1,
+                               C2, h * u, w * u);
+    });
+    if (!built) return MDX_ERR_BAD_SHAPE;
     if (dbias)
         hipLaunchKernelGGL(decoder_glue_bias_finish_kernel, dim3(C1), dim3(64), 0, st, bias_part, B, C1,
                            (int)(graw_grid.x * graw_grid.y), dbias);
@@ -383,23 +355,16 @@ MDX_EXPORT int mdx_maxpool3s2_fwd(const void *in, void *out, uint8_t *arg, int B
     if (BC <= 0 || BC > 65535 || H <= 0 || W <= 0) return MDX_ERR_BAD_SHAPE;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;   // floor((H + 2 - 3) / 2) + 1
     const dim3 grid = grid3(Wo, Ho, BC), block(GX, GY);
-    if (dtype != MDX_F32 && dtype != MDX_BF16) return MDX_ERR_BAD_SHAPE;
-    if (W % 4 == 0) {      // rows 16-byte (8-byte for bf16) aligned, Wo even: two outputs per thread
-        const dim3 grid2 = grid3(Wo / 2, Ho, BC);
-        if (dtype == MDX_F32)
-            hipLaunchKernelGGL((maxpool3s2_fwd2_kernel<float>), grid2, block, 0, (hipStream_t)stream, (const float *)in,
-                               (float *)out, arg, H, W, Ho, Wo);
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (W % 4 == 0)        // rows 16-byte (8-byte for bf16) aligned, Wo even: two outputs per thread
+            hipLaunchKernelGGL((maxpool3s2_fwd2_kernel<T>), grid3(Wo / 2, Ho, BC), block, 0, (hipStream_t)stream, (const T *)in,
+                               (T *)out, arg, H, W, Ho, Wo);
         else
-            hipLaunchKernelGGL((maxpool3s2_fwd2_kernel<bf16>), grid2, block, 0, (hipStream_t)stream, (const bf16 *)in,
-                               (bf16 *)out, arg, H, W, Ho, Wo);
-        return check_launch();
-    }
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((maxpool3s2_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float *)in,
-                           (float *)out, arg, H, W, Ho, Wo);
-    else
-        hipLaunchKernelGGL((maxpool3s2_fwd_kernel<bf16>), grid, block, 0, (hipStream_t)stream, (const bf16 *)in,
-                           (bf16 *)out, arg, H, W, Ho, Wo);
+            hipLaunchKernelGGL((maxpool3s2_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)in, (T *)out, arg, H, W,
+                               Ho, Wo);
+    });
     return check_launch();
 }
 
@@ -410,13 +375,11 @@ MDX_EXPORT int mdx_maxpool3s2_bwd(const void *gout, const uint8_t *arg, void *gi
     if (BC <= 0 || BC > 65535 || H <= 0 || W <= 0) return MDX_ERR_BAD_SHAPE;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const dim3 grid = grid3((W + 1) / 2, (H + 1) / 2, BC), block(GX, GY);
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((maxpool3s2_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float *)gout, arg,
-                           (float *)gin, H, W, Ho, Wo);
-    else if (dtype == MDX_BF16)
-        hipLaunchKernelGGL((maxpool3s2_bwd_kernel<bf16>), grid, block, 0, (hipStream_t)stream, (const bf16 *)gout, arg,
-                           (bf16 *)gin, H, W, Ho, Wo);
-    else
-        return MDX_ERR_BAD_SHAPE;
+    const bool built = dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((maxpool3s2_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)gout, arg, (T *)gin, H, W, Ho,
+                           Wo);
+    });
+    if (!built) return MDX_ERR_BAD_SHAPE;
     return check_launch();
 }

@@ -335,7 +335,6 @@ __global__ __launch_bounds__(NB) void maxpool3s2_nhwc_bwd_kernel(const T *__rest
     store_vec<T, N>(gin + ((size_t)blockIdx.x * W + x) * C + c0, o);
 }
 
-static inline int vec_elems(int dtype) { return dtype == 0 ? 4 : 8; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace nhwc
@@ -343,8 +342,6 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 using namespace mdx;
 using namespace mdx::nhwc;
-
-enum { MDX_F32 = 0, MDX_BF16 = 1 };
 
 static int glue_shape_ok(int B, int C1, int C2, int h, int w, int upsample, int in_dtype)
 {
@@ -361,33 +358,29 @@ MDX_EXPORT int mdx_decoder_glue_nhwc_fwd(const void *raw, const void *skip, cons
                                          int h, int w, int upsample, int elu, int in_dtype, int out_dtype, void *stream)
 {
     if (!raw || !out || (C2 > 0 && !skip)) return MDX_ERR_NULL_POINTER;
-    if ((in_dtype != MDX_F32 && in_dtype != MDX_BF16) || (out_dtype != MDX_F32 && out_dtype != MDX_BF16)) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return MDX_ERR_BAD_SHAPE;
     const int bad = glue_shape_ok(B, C1, C2, h, w, upsample, in_dtype);
     if (bad) return bad;
-    const size_t out_align = (size_t)vec_elems(in_dtype) * (out_dtype == MDX_F32 ? 4 : 2);   // one channel vector of `out`
+    const size_t out_align = vec_elems(in_dtype) * elem_bytes(out_dtype);   // one channel vector of `out`
     if (!aligned(raw, 16) || !aligned(out, out_align) || (skip && !aligned(skip, 16))) return MDX_ERR_MISALIGNED;
     const int u = upsample ? 2 : 1, Hp = h * u + 2, Wp = w * u + 2;
     const Tile t = make_tile(C1 + C2, vec_elems(in_dtype));
     const dim3 grid(ceil_div(B * Hp, RPT), ceil_div(Wp, t.PL), t.ny), block(NB);
     if (grid.y > 65535 || grid.z > 65535) return MDX_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == MDX_F32 && out_dtype == MDX_F32)
-        hipLaunchKernelGGL((decoder_glue_nhwc_fwd_kernel<float, float>), grid, block, 0, st, (const float *)raw, (const float *)skip,
-                           bias, (float *)out, B, C1, C2, h, w, upsample, elu, t.CVB, t.PL);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_BF16)
-        hipLaunchKernelGGL((decoder_glue_nhwc_fwd_kernel<bf16, bf16>), grid, block, 0, st, (const bf16 *)raw, (const bf16 *)skip,
-                           bias, (bf16 *)out, B, C1, C2, h, w, upsample, elu, t.CVB, t.PL);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_F32)
-        hipLaunchKernelGGL((decoder_glue_nhwc_fwd_kernel<bf16, float>), grid, block, 0, st, (const bf16 *)raw, (const bf16 *)skip,
-                           bias, (float *)out, B, C1, C2, h, w, upsample, elu, t.CVB, t.PL);
-    else
-        return MDX_ERR_BAD_SHAPE;
+    const bool built = dispatch_dtype_pair(in_dtype, out_dtype, [&](auto ti, auto to) {
+        using TI = typename decltype(ti)::type;
+        using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL((decoder_glue_nhwc_fwd_kernel<TI, TO>), grid, block, 0, st, (const TI *)raw, (const TI *)skip, bias, (TO *)out,
+                           B, C1, C2, h, w, upsample, elu, t.CVB, t.PL);
+    });
+    if (!built) return MDX_ERR_BAD_SHAPE;
     return check_launch();
 }
 
 MDX_EXPORT size_t mdx_decoder_glue_nhwc_workspace_bytes(int B, int C1, int h, int w, int in_dtype)
 {
-    if (B <= 0 || C1 <= 0 || h <= 0 || w <= 0 || (in_dtype != MDX_F32 && in_dtype != MDX_BF16) || C1 % vec_elems(in_dtype)) return 0;
+    if (B <= 0 || C1 <= 0 || h <= 0 || w <= 0 || !dtype_ok(in_dtype) || C1 % vec_elems(in_dtype)) return 0;
     const Tile t = make_tile(C1, vec_elems(in_dtype));
     return (size_t)ceil_div(B * h, RPT) * ceil_div(w, t.PL) * C1 * sizeof(float);
 }
@@ -397,11 +390,11 @@ MDX_EXPORT int mdx_decoder_glue_nhwc_bwd(const void *gout, const void *raw, cons
                                          int out_dtype, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!gout || !raw || !graw || (C2 > 0 && !gskip)) return MDX_ERR_NULL_POINTER;
-    if ((in_dtype != MDX_F32 && in_dtype != MDX_BF16) || (out_dtype != MDX_F32 && out_dtype != MDX_BF16)) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return MDX_ERR_BAD_SHAPE;
     const int bad = glue_shape_ok(B, C1, C2, h, w, upsample, in_dtype);
     if (bad) return bad;
     if (dbias && (!workspace || workspace_bytes < mdx_decoder_glue_nhwc_workspace_bytes(B, C1, h, w, in_dtype))) return MDX_ERR_WORKSPACE;
-    const size_t out_align = (size_t)vec_elems(in_dtype) * (out_dtype == MDX_F32 ? 4 : 2);
+    const size_t out_align = vec_elems(in_dtype) * elem_bytes(out_dtype);
     if (!aligned(gout, out_align) || !aligned(raw, 16) || !aligned(graw, 16) || (gskip && !aligned(gskip, 16))) return MDX_ERR_MISALIGNED;
     float *bias_part = dbias ? (float *)workspace : nullptr;
     const int u = upsample ? 2 : 1, N = vec_elems(in_dtype);
@@ -409,26 +402,21 @@ MDX_EXPORT int mdx_decoder_glue_nhwc_bwd(const void *gout, const void *raw, cons
     const dim3 block(NB), graw_grid(ceil_div(B * h, RPT), ceil_div(w, t1.PL), t1.ny);
     if (graw_grid.y > 65535) return MDX_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-#define MDX_GLUE_BWD(TI, TO)                                                                                                     \
-    do {                                                                                                                         \
-        if (upsample)                                                                                                            \
-            hipLaunchKernelGGL((decoder_glue_nhwc_bwd_raw_kernel<TI, TO, 2>), graw_grid, block, 0, st, (const TO *)gout,         \
-                               (const TI *)raw, bias, (TI *)graw, bias_part, B, C1, C2, h, w, elu, t1.CVB, t1.PL);                \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((decoder_glue_nhwc_bwd_raw_kernel<TI, TO, 1>), graw_grid, block, 0, st, (const TO *)gout,         \
-                               (const TI *)raw, bias, (TI *)graw, bias_part, B, C1, C2, h, w, elu, t1.CVB, t1.PL);                \
-        if (C2 > 0) {                                                                                                            \
-            const Tile t2 = make_tile(C2, N);                                                                                    \
-            const dim3 gskip_grid(ceil_div(B * h * u, RPT), ceil_div(w * u, t2.PL), t2.ny);                                      \
-            hipLaunchKernelGGL((decoder_glue_nhwc_bwd_skip_kernel<TI, TO>), gskip_grid, block, 0, st, (const TO *)gout,          \
-                               (TI *)gskip, B, C1, C2, h * u, w * u, t2.CVB, t2.PL);                                              \
-        }                                                                                                                        \
-    } while (0)
-    if (in_dtype == MDX_F32 && out_dtype == MDX_F32) MDX_GLUE_BWD(float, float);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_BF16) MDX_GLUE_BWD(bf16, bf16);
-    else if (in_dtype == MDX_BF16 && out_dtype == MDX_F32) MDX_GLUE_BWD(bf16, float);
-    else return MDX_ERR_BAD_SHAPE;
-#undef MDX_GLUE_BWD
+    const bool built = dispatch_dtype_pair(in_dtype, out_dtype, [&](auto ti, auto to) {
+        using TI = typename decltype(ti)::type;
+        using TO = typename decltype(to)::type;
+        dispatch_flag(upsample != 0, [&](auto up) {
+            hipLaunchKernelGGL((decoder_glue_nhwc_bwd_raw_kernel<TI, TO, decltype(up)::value ? 2 : 1>), graw_grid, block, 0, st,
+                               (const TO *)gout, (const TI *)raw, bias, (TI *)graw, bias_part, B, C1, C2, h, w, elu, t1.CVB, t1.PL);
+        });
+        if (C2 > 0) {
+            const Tile t2 = make_tile(C2, N);
+            const dim3 gskip_grid(ceil_div(B * h * u, RPT), ceil_div(w * u, t2.PL), t2.ny);
+            hipLaunchKernelGGL((decoder_glue_nhwc_bwd_skip_kernel<TI, TO>), gskip_grid, block, 0, st, (const TO *)gout, (TI *)gskip, B,
+                               C1, C2, h * u, w * u, t2.CVB, t2.PL);
+        }
+    });
+    if (!built) return MDX_ERR_BAD_SHAPE;
     if (dbias)
         hipLaunchKernelGGL(colsum_finish_kernel, dim3(ceil_div(C1, CS_C)), dim3(CS_C * CS_S), 0, st, bias_part,
                            (int)(graw_grid.x * graw_grid.y), C1, dbias);
@@ -440,7 +428,7 @@ MDX_EXPORT int mdx_maxpool3s2_nhwc_fwd(const void *in, void *out, uint8_t *arg, 
                                        void *stream)
 {
     if (!in || !out || !arg) return MDX_ERR_NULL_POINTER;
-    if (dtype != MDX_F32 && dtype != MDX_BF16) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || C % vec_elems(dtype)) return MDX_ERR_BAD_SHAPE;
     if (!aligned(in, 16) || !aligned(out, 16) || !aligned(arg, 8)) return MDX_ERR_MISALIGNED;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;   // floor((H + 2 - 3) / 2) + 1
@@ -448,12 +436,11 @@ MDX_EXPORT int mdx_maxpool3s2_nhwc_fwd(const void *in, void *out, uint8_t *arg, 
     const Tile t = make_tile(C, vec_elems(dtype));
     const dim3 grid(B * Ho, ceil_div(Wo, t.PL), t.ny), block(NB);
     if (grid.y > 65535) return MDX_ERR_BAD_SHAPE;
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((maxpool3s2_nhwc_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float *)in, (float *)out,
-                           arg, C, H, W, Ho, Wo, t.CVB, t.PL);
-    else
-        hipLaunchKernelGGL((maxpool3s2_nhwc_fwd_kernel<bf16>), grid, block, 0, (hipStream_t)stream, (const bf16 *)in, (bf16 *)out,
-                           arg, C, H, W, Ho, Wo, t.CVB, t.PL);
+    dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((maxpool3s2_nhwc_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)in, (T *)out, arg, C, H, W,
+                           Ho, Wo, t.CVB, t.PL);
+    });
     return check_launch();
 }
 
@@ -462,7 +449,7 @@ MDX_EXPORT int mdx_maxpool3s2_nhwc_bwd(const void *gout, const void *gout2, cons
 {
     if (!gout || !arg || !gin) return MDX_ERR_NULL_POINTER;
     if (gout2 && !aligned(gout2, 16)) return MDX_ERR_MISALIGNED;
-    if (dtype != MDX_F32 && dtype != MDX_BF16) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || C % vec_elems(dtype)) return MDX_ERR_BAD_SHAPE;
     if (!aligned(gout, 16) || !aligned(gin, 16) || !aligned(arg, 8)) return MDX_ERR_MISALIGNED;
     if ((long long)B * H >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
@@ -470,11 +457,10 @@ MDX_EXPORT int mdx_maxpool3s2_nhwc_bwd(const void *gout, const void *gout2, cons
     const Tile t = make_tile(C, vec_elems(dtype));
     const dim3 grid(B * H, ceil_div(W, t.PL), t.ny), block(NB);
     if (grid.y > 65535) return MDX_ERR_BAD_SHAPE;
-    if (dtype == MDX_F32)
-        hipLaunchKernelGGL((maxpool3s2_nhwc_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float *)gout,
-                           (const float *)gout2, arg, (float *)gin, C, H, W, Ho, Wo, t.CVB, t.PL);
-    else
-        hipLaunchKernelGGL((maxpool3s2_nhwc_bwd_kernel<bf16>), grid, block, 0, (hipStream_t)stream, (const bf16 *)gout,
-                           (const bf16 *)gout2, arg, (bf16 *)gin, C, H, W, Ho, Wo, t.CVB, t.PL);
+    dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((maxpool3s2_nhwc_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)gout, (const T *)gout2, arg,
+                           (T *)gin, C, H, W, Ho, Wo, t.CVB, t.PL);
+    });
     return check_launch();
 }

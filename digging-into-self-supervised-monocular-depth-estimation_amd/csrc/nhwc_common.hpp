@@ -4,26 +4,14 @@
 // channel vector (4 float32 / 8 bfloat16) of one pixel: a 256-thread block is CVB channel vectors wide and
 // PL = 256 / CVB pixels deep, so a wave reads whole 128-byte lines whatever C is (C = 64 float32: 4 pixels per wave).
 #pragma once
-#include "mdx_common.hpp"
-#include <stdint.h>
+#include "mdx_dtype.hpp"
 
 namespace mdx {
 namespace nhwc {
 
-struct bf16 { uint16_t v; };
-
-__device__ __forceinline__ float to_float(float x) { return x; }
-__device__ __forceinline__ float to_float(bf16 x) { return __uint_as_float((uint32_t)x.v << 16); }
-template <typename T> __device__ __forceinline__ T from_float(float x);
-template <> __device__ __forceinline__ float from_float<float>(float x) { return x; }
-template <> __device__ __forceinline__ bf16 from_float<bf16>(float x)
-{
-    // round to nearest even, NaN stays NaN (torch's float -> bfloat16): gfx950's v_cvt_pk_bf16_f32 -- one instruction where the
-    // integer sequence (NaN test, rounding add, shift) took six, which made the bfloat16 apply passes VALU-bound
-    bf16 r;
-    r.v = __builtin_bit_cast(uint16_t, (__bf16)x);
-    return r;
-}
+using mdx::bf16;
+using mdx::to_float;
+template <typename T> __device__ __forceinline__ T from_float(float x) { return from_float_cvt<T>(x); }     // the hardware conversion (mdx_dtype.hpp)
 
 constexpr int NB = 256;                                   // threads per block
 

@@ -13,22 +13,13 @@
 // formed in float64).  Statistics are those of torch.nn.functional.batch_norm: biased variance to normalise,
 // unbiased for running_var, running = (1 - momentum) * running + momentum * batch.
 // ReLU mask in the backward comes from y > 0 (y is alive anyway: the next convolution saved it).
-#include "mdx_common.hpp"
-#include <stdint.h>
+#include "mdx_dtype.hpp"
 
 namespace mdx {
 
-struct bf16n { uint16_t v; };
-__device__ __forceinline__ float ld(const float *p, size_t i) { return p[i]; }
-__device__ __forceinline__ float ld(const bf16n *p, size_t i) { return __uint_as_float((uint32_t)p[i].v << 16); }
-__device__ __forceinline__ void st(float *p, size_t i, float x) { p[i] = x; }
-__device__ __forceinline__ void st(bf16n *p, size_t i, float x)
-{
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) { p[i].v = (uint16_t)((u >> 16) | 0x40u); return; }
-    u += 0x7fffu + ((u >> 16) & 1u);
-    p[i].v = (uint16_t)(u >> 16);
-}
+// element i of a map as float32, and back (planar kernels: the integer conversion, mdx_dtype.hpp)
+template <typename T> __device__ __forceinline__ float ld(const T *p, size_t i) { return to_float(p[i]); }
+template <typename T> __device__ __forceinline__ void st(T *p, size_t i, float x) { p[i] = from_float_int<T>(x); }
 
 constexpr int NB = 256;          // threads per block
 constexpr int VEC = 4;           // elements per thread and access
@@ -36,7 +27,7 @@ constexpr int SPAN = 8192;       // elements of one plane a block owns (8 access
 
 template <typename T> struct Vec4 { T v[VEC]; };
 template <> struct __attribute__((aligned(16))) Vec4<float> { float v[VEC]; };
-template <> struct __attribute__((aligned(8))) Vec4<bf16n> { bf16n v[VEC]; };
+template <> struct __attribute__((aligned(8))) Vec4<bf16> { bf16 v[VEC]; };
 
 // the span [lo, hi) of plane (b, c) this block owns; grid = (C, B * K), K spans per plane
 struct SpanId { int c, b, lo, hi; size_t plane; };
@@ -399,14 +390,8 @@ __global__ __launch_bounds__(NTH) void bn_small_bwd_kernel(const T *__restrict__
     }
 }
 
-// the small-map kernels in their 256- or 1024-thread form by the channel's element count
-#define MDX_BN_SMALL(kind, T, ...)                                                                                   \
-    do {                                                                                                             \
-        if ((long long)B * HW <= (long long)SB_TINY * 2 * VEC)                                                       \
-            hipLaunchKernelGGL((bn_small_##kind##_kernel<T, SB_TINY>), dim3(C), dim3(SB_TINY), 0, st, __VA_ARGS__);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((bn_small_##kind##_kernel<T, SB>), dim3(C), dim3(SB), 0, st, __VA_ARGS__);            \
-    } while (0)
+// the small-map kernels run in their 256- or 1024-thread form by the channel's element count
+static inline bool tiny_map(int B, int HW) { return (long long)B * HW <= (long long)SB_TINY * 2 * VEC; }
 static inline bool small_map(int B, int HW) { return (HW % VEC) == 0 && (long long)B * HW <= SMALL_MAX; }
 
 static inline int spans_per_plane(int HW) { return (HW + SPAN - 1) / SPAN; }
@@ -430,39 +415,34 @@ MDX_EXPORT int mdx_bn_act_fwd(const void *x, const void *res, const float *gamma
     if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !workspace) return MDX_ERR_NULL_POINTER;
     if ((run_mean == nullptr) != (run_var == nullptr)) return MDX_ERR_NULL_POINTER;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || (long long)H * W > (1ll << 30)) return MDX_ERR_BAD_SHAPE;
-    if (dtype != 0 && dtype != 1) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     const int HW = H * W, K = spans_per_plane(HW);
     if ((long long)B * K > 65535) return MDX_ERR_BAD_SHAPE;
     if (workspace_bytes < mdx_bn_workspace_bytes(B, C, H, W)) return MDX_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (small_map(B, HW)) {
-        if (dtype == 0)
-            MDX_BN_SMALL(fwd, float, gamma, beta, C, HW, B, eps, momentum,
-                               relu, (float *)y, save_mean, save_invstd, run_mean, run_var, (const float *)x,
-                               (const float *)res, groups);
-        else
-            MDX_BN_SMALL(fwd, bf16n, gamma, beta, C, HW, B, eps, momentum,
-                               relu, (bf16n *)y, save_mean, save_invstd, run_mean, run_var, (const bf16n *)x,
-                               (const bf16n *)res, groups);
+        dispatch_dtype_flag(dtype, tiny_map(B, HW), [&](auto t, auto tiny) {
+            using T = typename decltype(t)::type;
+            constexpr int NTH = decltype(tiny)::value ? SB_TINY : SB;
+            hipLaunchKernelGGL((bn_small_fwd_kernel<T, NTH>), dim3(C), dim3(NTH), 0, st, gamma, beta, C, HW, B, eps, momentum, relu,
+                               (T *)y, save_mean, save_invstd, run_mean, run_var, (const T *)x, (const T *)res, groups);
+        });
         return check_launch();
     }
     const dim3 grid(C, B * K), block(NB);
     float *part = (float *)workspace;
-    const size_t gelems = (size_t)B * C * HW, esize = dtype == 0 ? 4 : 2;
+    const size_t gelems = (size_t)B * C * HW, esize = elem_bytes(dtype);
     for (int g = 0; g < groups; ++g) {   // sub-batches in order (running statistics): stream order does that
         const char *xg = (const char *)x + g * gelems * esize;
         const char *rg = res ? (const char *)res + g * gelems * esize : nullptr;
         char *yg = (char *)y + g * gelems * esize;
         float *sm = save_mean + (size_t)g * C, *si = save_invstd + (size_t)g * C;
-        if (dtype == 0) {
-            hipLaunchKernelGGL((bn_fwd_stats_kernel<float>), grid, block, 0, st, (const float *)xg, C, HW, K, part);
-            hipLaunchKernelGGL((bn_fwd_apply_kernel<float>), grid, block, 0, st, (const float *)xg, (const float *)rg, gamma,
-                               beta, part, C, HW, K, B, eps, momentum, relu, (float *)yg, sm, si, run_mean, run_var);
-        } else {
-            hipLaunchKernelGGL((bn_fwd_stats_kernel<bf16n>), grid, block, 0, st, (const bf16n *)xg, C, HW, K, part);
-            hipLaunchKernelGGL((bn_fwd_apply_kernel<bf16n>), grid, block, 0, st, (const bf16n *)xg, (const bf16n *)rg, gamma,
-                               beta, part, C, HW, K, B, eps, momentum, relu, (bf16n *)yg, sm, si, run_mean, run_var);
-        }
+        dispatch_dtype(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((bn_fwd_stats_kernel<T>), grid, block, 0, st, (const T *)xg, C, HW, K, part);
+            hipLaunchKernelGGL((bn_fwd_apply_kernel<T>), grid, block, 0, st, (const T *)xg, (const T *)rg, gamma, beta, part, C, HW, K,
+                               B, eps, momentum, relu, (T *)yg, sm, si, run_mean, run_var);
+        });
     }
     return check_launch();
 }
@@ -475,44 +455,36 @@ MDX_EXPORT int mdx_bn_act_bwd(const void *dy, const void *y, const void *x, cons
     if (!dy || !y || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace)
         return MDX_ERR_NULL_POINTER;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || (long long)H * W > (1ll << 30)) return MDX_ERR_BAD_SHAPE;
-    if (dtype != 0 && dtype != 1) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     const int HW = H * W, K = spans_per_plane(HW);
     if ((long long)B * K > 65535) return MDX_ERR_BAD_SHAPE;
     if (workspace_bytes < mdx_bn_workspace_bytes(B, C, H, W)) return MDX_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (small_map(B, HW)) {
-        if (dtype == 0)
-            MDX_BN_SMALL(bwd, float, (const float *)dy, (const float *)y,
-                               (const float *)x, gamma, save_mean, save_invstd, C, HW, B, relu, 0, (float *)dx,
-                               (float *)dres, dgamma, dbeta, groups);
-        else
-            MDX_BN_SMALL(bwd, bf16n, (const bf16n *)dy, (const bf16n *)y,
-                               (const bf16n *)x, gamma, save_mean, save_invstd, C, HW, B, relu, 0, (bf16n *)dx,
-                               (bf16n *)dres, dgamma, dbeta, groups);
+        dispatch_dtype_flag(dtype, tiny_map(B, HW), [&](auto t, auto tiny) {
+            using T = typename decltype(t)::type;
+            constexpr int NTH = decltype(tiny)::value ? SB_TINY : SB;
+            hipLaunchKernelGGL((bn_small_bwd_kernel<T, NTH>), dim3(C), dim3(NTH), 0, st, (const T *)dy, (const T *)y, (const T *)x,
+                               gamma, save_mean, save_invstd, C, HW, B, relu, 0, (T *)dx, (T *)dres, dgamma, dbeta, groups);
+        });
         return check_launch();
     }
     const dim3 grid(C, B * K), block(NB);
     float *part = (float *)workspace;
-    const size_t gelems = (size_t)B * C * HW, esize = dtype == 0 ? 4 : 2;
+    const size_t gelems = (size_t)B * C * HW, esize = elem_bytes(dtype);
     for (int g = 0; g < groups; ++g) {
         const char *dyg = (const char *)dy + g * gelems * esize, *yg = (const char *)y + g * gelems * esize;
         const char *xg = (const char *)x + g * gelems * esize;
         char *dxg = (char *)dx + g * gelems * esize;
         char *drg = dres ? (char *)dres + g * gelems * esize : nullptr;
         const float *sm = save_mean + (size_t)g * C, *si = save_invstd + (size_t)g * C;
-        if (dtype == 0) {
-            hipLaunchKernelGGL((bn_bwd_stats_kernel<float>), grid, block, 0, st, (const float *)dyg, (const float *)yg,
-                               (const float *)xg, sm, si, C, HW, K, relu, part);
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), grid, block, 0, st, (const float *)dyg, (const float *)yg,
-                               (const float *)xg, gamma, sm, si, part, C, HW, K, B, relu, g > 0, (float *)dxg,
-                               (float *)drg, dgamma, dbeta);
-        } else {
-            hipLaunchKernelGGL((bn_bwd_stats_kernel<bf16n>), grid, block, 0, st, (const bf16n *)dyg, (const bf16n *)yg,
-                               (const bf16n *)xg, sm, si, C, HW, K, relu, part);
-            hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16n>), grid, block, 0, st, (const bf16n *)dyg, (const bf16n *)yg,
-                               (const bf16n *)xg, gamma, sm, si, part, C, HW, K, B, relu, g > 0, (bf16n *)dxg,
-                               (bf16n *)drg, dgamma, dbeta);
-        }
+        dispatch_dtype(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((bn_bwd_stats_kernel<T>), grid, block, 0, st, (const T *)dyg, (const T *)yg, (const T *)xg, sm, si, C,
+                               HW, K, relu, part);
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), grid, block, 0, st, (const T *)dyg, (const T *)yg, (const T *)xg, gamma, sm,
+                               si, part, C, HW, K, B, relu, g > 0, (T *)dxg, (T *)drg, dgamma, dbeta);
+        });
     }
     return check_launch();
 }

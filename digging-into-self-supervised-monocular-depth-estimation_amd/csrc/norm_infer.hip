@@ -135,17 +135,6 @@ __global__ __launch_bounds__(NB) void bn_infer_planar_kernel(const T *__restrict
     }
 }
 
-static inline int vec_elems(int dtype) { return dtype == 0 ? 4 : 8; }
-
-// pointers and sizes every form needs
-static int common_args_ok(const void *x, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
-                          const void *y, int B, int C, int H, int W, int dtype)
-{
-    if (!x || !gamma || !beta || !run_mean || !run_var || !y) return MDX_ERR_NULL_POINTER;
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (dtype != 0 && dtype != 1)) return MDX_ERR_BAD_SHAPE;
-    return MDX_OK;
-}
-
 }  // namespace infer
 }  // namespace mdx
 
@@ -157,23 +146,22 @@ MDX_EXPORT int mdx_bn_act_infer(const void *x, const void *res, const float *gam
                                 const float *run_var, void *y, int B, int C, int H, int W, float eps, int relu, int dtype,
                                 void *stream)
 {
-    const int bad = common_args_ok(x, gamma, beta, run_mean, run_var, y, B, C, H, W, dtype);
-    if (bad) return bad;
+    if (!x || !gamma || !beta || !run_mean || !run_var || !y) return MDX_ERR_NULL_POINTER;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     if ((long long)H * W >= (1ll << 31) || (long long)B * C >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
     const int HW = H * W, spans = (HW + SPAN - 1) / SPAN;
     if (spans > 65535) return MDX_ERR_BAD_SHAPE;
-    const size_t es = dtype == 0 ? 4 : 2;
+    const size_t es = elem_bytes(dtype);
     if (!aligned(x, es) || !aligned(y, es) || (res && !aligned(res, es))) return MDX_ERR_MISALIGNED;
     const uintptr_t mx = (uintptr_t)x & 15;
     const int vec = ((uintptr_t)y & 15) == mx && (!res || ((uintptr_t)res & 15) == mx);
     const dim3 grid((unsigned)(B * C), spans), block(NB);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((bn_infer_planar_kernel<float>), grid, block, 0, st, (const float *)x, (const float *)res, gamma, beta,
-                           run_mean, run_var, eps, C, HW, relu, vec, (float *)y);
-    else
-        hipLaunchKernelGGL((bn_infer_planar_kernel<bf16>), grid, block, 0, st, (const bf16 *)x, (const bf16 *)res, gamma, beta,
-                           run_mean, run_var, eps, C, HW, relu, vec, (bf16 *)y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_infer_planar_kernel<T>), grid, block, 0, st, (const T *)x, (const T *)res, gamma, beta, run_mean,
+                           run_var, eps, C, HW, relu, vec, (T *)y);
+    });
     return check_launch();
 }
 
@@ -181,20 +169,18 @@ MDX_EXPORT int mdx_bn_act_nhwc_infer(const void *x, const void *res, const float
                                      const float *run_var, void *y, int B, int C, int H, int W, float eps, int relu, int dtype,
                                      void *stream)
 {
-    const int bad = common_args_ok(x, gamma, beta, run_mean, run_var, y, B, C, H, W, dtype);
+    if (!x || !gamma || !beta || !run_mean || !run_var || !y) return MDX_ERR_NULL_POINTER;
+    const int bad = nhwc_map_ok(B, C, H, W, dtype);
     if (bad) return bad;
-    if (C % vec_elems(dtype)) return MDX_ERR_BAD_SHAPE;                  // a thread owns a whole 16-byte channel vector
-    if ((long long)B * H * W >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
     if (!aligned(x, 16) || !aligned(y, 16) || (res && !aligned(res, 16))) return MDX_ERR_MISALIGNED;
     const int M = B * H * W, N = vec_elems(dtype);
     const nhwc::Rows g = nhwc::make_rows(M, C, N, MAX_BLOCKS, ITERS);
     const dim3 grid(g.nblk, g.t.ny), block(NB);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((bn_infer_nhwc_kernel<float>), grid, block, 0, st, (const float *)x, (const float *)res, gamma, beta,
-                           run_mean, run_var, eps, M, C, g.t.CVB, g.t.PL, g.RB, relu, (float *)y);
-    else
-        hipLaunchKernelGGL((bn_infer_nhwc_kernel<bf16>), grid, block, 0, st, (const bf16 *)x, (const bf16 *)res, gamma, beta,
-                           run_mean, run_var, eps, M, C, g.t.CVB, g.t.PL, g.RB, relu, (bf16 *)y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_infer_nhwc_kernel<T>), grid, block, 0, st, (const T *)x, (const T *)res, gamma, beta, run_mean,
+                           run_var, eps, M, C, g.t.CVB, g.t.PL, g.RB, relu, (T *)y);
+    });
     return check_launch();
 }

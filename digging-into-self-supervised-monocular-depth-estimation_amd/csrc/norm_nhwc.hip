@@ -30,7 +30,7 @@ constexpr int STATS_BWD_BLOCKS_F32 = 256, STATS_BWD_BLOCKS_BF16 = 384;
 constexpr int STATS_MAX_BLOCKS = 384;      // the largest of the three: sizes the workspace and the finalize pass's unrolled loads
 constexpr int APPLY_MAX_BLOCKS = 4096;
 constexpr int STATS_ITERS = 8, APPLY_ITERS = 4;          // row sweeps a block is given at least (small maps: fewer blocks)
-static inline int stats_bwd_blocks(int dtype) { return dtype == 0 ? STATS_BWD_BLOCKS_F32 : STATS_BWD_BLOCKS_BF16; }
+static inline int stats_bwd_blocks(int dtype) { return dtype == MDX_F32 ? STATS_BWD_BLOCKS_F32 : STATS_BWD_BLOCKS_BF16; }
 
 // ---- forward, pass 1 ----------------------------------------------------------------------------------------------
 template <typename T>
@@ -337,8 +337,6 @@ __global__ __launch_bounds__(NB) void bn_nhwc_bwd_apply_kernel(const T *__restri
     }
 }
 
-static inline int vec_elems(int dtype) { return dtype == 0 ? 4 : 8; }
-
 }  // namespace nhwc
 }  // namespace mdx
 
@@ -348,18 +346,15 @@ using namespace mdx::nhwc;
 // workspace: block partials [groups][STATS blocks][2][C] + backward totals [groups][2][C], float32
 MDX_EXPORT size_t mdx_bn_nhwc_workspace_bytes(int B, int C, int H, int W, int groups, int dtype)
 {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || (dtype != 0 && dtype != 1)) return 0;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || !dtype_ok(dtype)) return 0;
     const Rows g = make_rows((long long)B * H * W, C, vec_elems(dtype), STATS_MAX_BLOCKS, STATS_ITERS);
     return ((size_t)groups * g.nblk * 2 * C + (size_t)groups * 2 * C) * sizeof(float);
 }
 
 static int nhwc_args_ok(int B, int C, int H, int W, int groups, int dtype)
 {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || groups > 65535) return MDX_ERR_BAD_SHAPE;
-    if (dtype != 0 && dtype != 1) return MDX_ERR_BAD_SHAPE;
-    if (C % vec_elems(dtype)) return MDX_ERR_BAD_SHAPE;                       // a thread owns a whole 16-byte channel vector
-    if ((long long)B * H * W >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
-    return MDX_OK;
+    if (groups <= 0 || groups > 65535) return MDX_ERR_BAD_SHAPE;              // grid.z
+    return nhwc_map_ok(B, C, H, W, dtype);
 }
 
 // x, res, y: [groups * B][H][W][C] (channels-last memory), dtype 0 float32 / 1 bfloat16; statistics and parameters float32.
@@ -380,18 +375,17 @@ MDX_EXPORT int mdx_bn_act_nhwc_fwd(const void *x, const void *res, const float *
     float *part = (float *)workspace;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid_s(gs.nblk, gs.t.ny, groups), grid_a(ga.nblk, ga.t.ny, groups), block(NB);
-    if (dtype == 0)
-        hipLaunchKernelGGL((bn_nhwc_fwd_stats_kernel<float>), grid_s, block, 0, st, (const float *)x, M, C, gs.t.CVB, gs.t.PL, gs.RB, part);
-    else
-        hipLaunchKernelGGL((bn_nhwc_fwd_stats_kernel<bf16>), grid_s, block, 0, st, (const bf16 *)x, M, C, gs.t.CVB, gs.t.PL, gs.RB, part);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_nhwc_fwd_stats_kernel<T>), grid_s, block, 0, st, (const T *)x, M, C, gs.t.CVB, gs.t.PL, gs.RB, part);
+    });
     hipLaunchKernelGGL(bn_nhwc_fwd_finalize_kernel, dim3((C + FC - 1) / FC), dim3(FC * FS), 0, st, part, gs.nblk, C, groups, (double)M,
                        eps, momentum, save_mean, save_invstd, run_mean, run_var);
-    if (dtype == 0)
-        hipLaunchKernelGGL((bn_nhwc_fwd_apply_kernel<float>), grid_a, block, 0, st, (const float *)x, (const float *)res, gamma, beta,
-                           save_mean, save_invstd, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (float *)y);
-    else
-        hipLaunchKernelGGL((bn_nhwc_fwd_apply_kernel<bf16>), grid_a, block, 0, st, (const bf16 *)x, (const bf16 *)res, gamma, beta,
-                           save_mean, save_invstd, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (bf16 *)y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_nhwc_fwd_apply_kernel<T>), grid_a, block, 0, st, (const T *)x, (const T *)res, gamma, beta, save_mean,
+                           save_invstd, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (T *)y);
+    });
     return check_launch();
 }
 
@@ -419,33 +413,18 @@ MDX_EXPORT int mdx_bn_act_nhwc_bwd(const void *dy, const void *dy2, const void *
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid_s(gs.nblk, gs.t.ny, groups), grid_a(ga.nblk, ga.t.ny, groups), block(NB);
     const bool maskx = !y;              // (checked above: only with relu, beta and no residual)
-#define MDX_BN_BWD(KERNEL, T, MX, ...) hipLaunchKernelGGL((KERNEL<T, MX>), __VA_ARGS__)
-    if (dtype == 0 && maskx)
-        MDX_BN_BWD(bn_nhwc_bwd_stats_kernel, float, true, grid_s, block, 0, st, (const float *)dy, (const float *)dy2, (const float *)y,
-                   (const float *)x, gamma, beta, save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part);
-    else if (dtype == 0)
-        MDX_BN_BWD(bn_nhwc_bwd_stats_kernel, float, false, grid_s, block, 0, st, (const float *)dy, (const float *)dy2, (const float *)y,
-                   (const float *)x, gamma, beta, save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part);
-    else if (maskx)
-        MDX_BN_BWD(bn_nhwc_bwd_stats_kernel, bf16, true, grid_s, block, 0, st, (const bf16 *)dy, (const bf16 *)dy2, (const bf16 *)y,
-                   (const bf16 *)x, gamma, beta, save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part);
-    else
-        MDX_BN_BWD(bn_nhwc_bwd_stats_kernel, bf16, false, grid_s, block, 0, st, (const bf16 *)dy, (const bf16 *)dy2, (const bf16 *)y,
-                   (const bf16 *)x, gamma, beta, save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part);
+    dispatch_dtype_flag(dtype, maskx, [&](auto t, auto mx) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_nhwc_bwd_stats_kernel<T, decltype(mx)::value>), grid_s, block, 0, st, (const T *)dy, (const T *)dy2,
+                           (const T *)y, (const T *)x, gamma, beta, save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part);
+    });
     hipLaunchKernelGGL(bn_nhwc_bwd_finalize_kernel, dim3((C + FC - 1) / FC), dim3(FC * FS), 0, st, part, gs.nblk, C, groups, (double)M, totals,
                        dgamma, dbeta);
-    if (dtype == 0 && maskx)
-        MDX_BN_BWD(bn_nhwc_bwd_apply_kernel, float, true, grid_a, block, 0, st, (const float *)dy, (const float *)dy2, (const float *)y,
-                   (const float *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (float *)dx, (float *)dres);
-    else if (dtype == 0)
-        MDX_BN_BWD(bn_nhwc_bwd_apply_kernel, float, false, grid_a, block, 0, st, (const float *)dy, (const float *)dy2, (const float *)y,
-                   (const float *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (float *)dx, (float *)dres);
-    else if (maskx)
-        MDX_BN_BWD(bn_nhwc_bwd_apply_kernel, bf16, true, grid_a, block, 0, st, (const bf16 *)dy, (const bf16 *)dy2, (const bf16 *)y,
-                   (const bf16 *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (bf16 *)dx, (bf16 *)dres);
-    else
-        MDX_BN_BWD(bn_nhwc_bwd_apply_kernel, bf16, false, grid_a, block, 0, st, (const bf16 *)dy, (const bf16 *)dy2, (const bf16 *)y,
-                   (const bf16 *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu, (bf16 *)dx, (bf16 *)dres);
-#undef MDX_BN_BWD
+    dispatch_dtype_flag(dtype, maskx, [&](auto t, auto mx) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_nhwc_bwd_apply_kernel<T, decltype(mx)::value>), grid_a, block, 0, st, (const T *)dy, (const T *)dy2,
+                           (const T *)y, (const T *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu,
+                           (T *)dx, (T *)dres);
+    });
     return check_launch();
 }

@@ -13,7 +13,6 @@
 namespace mdx {
 namespace nhwc {
 
-enum { PH_F32 = 0, PH_BF16 = 1 };
 constexpr int BA_BLOCKS = 256, BA_ITERS = 4;
 
 template <typename T>
@@ -145,12 +144,11 @@ __global__ __launch_bounds__(NB) void mean_bias_nhwc_bwd_kernel(const float *__r
     }
 }
 
-static inline int ph_vec(int dtype) { return dtype == PH_F32 ? 4 : 8; }
 static int ph_args_ok(long long M, int C, int dtype, bool vectors)
 {
-    if (dtype != PH_F32 && dtype != PH_BF16) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     if (M <= 0 || C <= 0 || M >= (1ll << 31) || M * C >= (1ll << 31)) return MDX_ERR_BAD_SHAPE;
-    if (vectors && C % ph_vec(dtype)) return MDX_ERR_BAD_SHAPE;
+    if (vectors && C % vec_elems(dtype)) return MDX_ERR_BAD_SHAPE;
     return MDX_OK;
 }
 
@@ -164,7 +162,7 @@ MDX_EXPORT size_t mdx_bias_act_nhwc_workspace_bytes(int B, int C, int H, int W, 
 {
     const long long M = (long long)B * H * W;
     if (ph_args_ok(M, C, dtype, true)) return 0;
-    return (size_t)make_rows(M, C, ph_vec(dtype), BA_BLOCKS, BA_ITERS).nblk * C * sizeof(float);
+    return (size_t)make_rows(M, C, vec_elems(dtype), BA_BLOCKS, BA_ITERS).nblk * C * sizeof(float);
 }
 
 MDX_EXPORT int mdx_bias_act_nhwc_fwd(const void *x, const float *bias, void *y, int B, int C, int H, int W, int relu, int dtype,
@@ -175,14 +173,13 @@ MDX_EXPORT int mdx_bias_act_nhwc_fwd(const void *x, const float *bias, void *y, 
     const int bad = ph_args_ok(M, C, dtype, true);
     if (bad) return bad;
     if (!aligned(x, 16) || !aligned(y, 16)) return MDX_ERR_MISALIGNED;
-    const Rows g = make_rows(M, C, ph_vec(dtype), 4096, BA_ITERS);
+    const Rows g = make_rows(M, C, vec_elems(dtype), 4096, BA_ITERS);
     const dim3 grid(g.nblk, g.t.ny), block(NB);
-    if (dtype == PH_F32)
-        hipLaunchKernelGGL((bias_act_nhwc_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float *)x, bias, (int)M, C,
-                           g.t.CVB, g.t.PL, g.RB, relu, (float *)y);
-    else
-        hipLaunchKernelGGL((bias_act_nhwc_fwd_kernel<bf16>), grid, block, 0, (hipStream_t)stream, (const bf16 *)x, bias, (int)M, C,
-                           g.t.CVB, g.t.PL, g.RB, relu, (bf16 *)y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bias_act_nhwc_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)x, bias, (int)M, C, g.t.CVB,
+                           g.t.PL, g.RB, relu, (T *)y);
+    });
     return check_launch();
 }
 
@@ -195,16 +192,15 @@ MDX_EXPORT int mdx_bias_act_nhwc_bwd(const void *dy, const void *y, void *dx, fl
     if (bad) return bad;
     if (!aligned(dy, 16) || !aligned(y, 16) || !aligned(dx, 16)) return MDX_ERR_MISALIGNED;
     if (workspace_bytes < mdx_bias_act_nhwc_workspace_bytes(B, C, H, W, dtype)) return MDX_ERR_WORKSPACE;
-    const Rows g = make_rows(M, C, ph_vec(dtype), BA_BLOCKS, BA_ITERS);
+    const Rows g = make_rows(M, C, vec_elems(dtype), BA_BLOCKS, BA_ITERS);
     const dim3 grid(g.nblk, g.t.ny), block(NB);
     float *part = (float *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PH_F32)
-        hipLaunchKernelGGL((bias_act_nhwc_bwd_kernel<float>), grid, block, 0, st, (const float *)dy, (const float *)y, (int)M, C, g.t.CVB,
-                           g.t.PL, g.RB, relu, (float *)dx, part);
-    else
-        hipLaunchKernelGGL((bias_act_nhwc_bwd_kernel<bf16>), grid, block, 0, st, (const bf16 *)dy, (const bf16 *)y, (int)M, C, g.t.CVB,
-                           g.t.PL, g.RB, relu, (bf16 *)dx, part);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bias_act_nhwc_bwd_kernel<T>), grid, block, 0, st, (const T *)dy, (const T *)y, (int)M, C, g.t.CVB, g.t.PL,
+                           g.RB, relu, (T *)dx, part);
+    });
     hipLaunchKernelGGL(colsum_scale_kernel, dim3((C + PF_C - 1) / PF_C), dim3(PF_C * PF_S), 0, st, part, g.nblk, C, 1.0f, dbias);
     return check_launch();
 }
@@ -218,12 +214,11 @@ MDX_EXPORT int mdx_mean_bias_nhwc_fwd(const void *x, const float *bias, float *o
     if (bad) return bad;
     const int n = B * C;
     const float inv = 1.0f / (float)HW;
-    if (dtype == PH_F32)
-        hipLaunchKernelGGL((mean_bias_nhwc_fwd_kernel<float>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, (const float *)x,
-                           bias, B, (int)HW, C, inv, scale, out);
-    else
-        hipLaunchKernelGGL((mean_bias_nhwc_fwd_kernel<bf16>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, (const bf16 *)x,
-                           bias, B, (int)HW, C, inv, scale, out);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((mean_bias_nhwc_fwd_kernel<T>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, (const T *)x, bias,
+                           B, (int)HW, C, inv, scale, out);
+    });
     return check_launch();
 }
 
@@ -236,12 +231,11 @@ MDX_EXPORT int mdx_mean_bias_nhwc_bwd(const float *gout, void *dx, float *dbias,
     if (bad) return bad;
     const int n = B * C;
     const float inv = 1.0f / (float)HW;
-    if (dtype == PH_F32)
-        hipLaunchKernelGGL((mean_bias_nhwc_bwd_kernel<float>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, gout, B, (int)HW, C,
-                           inv, scale, (float *)dx, dbias);
-    else
-        hipLaunchKernelGGL((mean_bias_nhwc_bwd_kernel<bf16>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, gout, B, (int)HW, C,
-                           inv, scale, (bf16 *)dx, dbias);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((mean_bias_nhwc_bwd_kernel<T>), dim3((n + NB - 1) / NB), dim3(NB), 0, (hipStream_t)stream, gout, B, (int)HW,
+                           C, inv, scale, (T *)dx, dbias);
+    });
     return check_launch();
 }
 
@@ -288,7 +282,7 @@ MDX_EXPORT int mdx_encoder_input_nhwc(const float *const *src, int blocks, int g
 {
     if (!src || !out) return MDX_ERR_NULL_POINTER;
     if (blocks < 1 || blocks > 2 || groups < 1 || groups > 2 || n <= 0 || H <= 0 || W <= 0) return MDX_ERR_BAD_SHAPE;
-    if (dtype != PH_F32 && dtype != PH_BF16) return MDX_ERR_BAD_SHAPE;
+    if (!dtype_ok(dtype)) return MDX_ERR_BAD_SHAPE;
     const long long total = (long long)blocks * n * H * W;
     if (total * 6 >= (1ll << 40)) return MDX_ERR_BAD_SHAPE;
     InputSrc s = {{nullptr, nullptr, nullptr, nullptr}};
@@ -299,11 +293,10 @@ MDX_EXPORT int mdx_encoder_input_nhwc(const float *const *src, int blocks, int g
         }
     if ((long long)H * W >= (1ll << 31) || blocks * n > 65535) return MDX_ERR_BAD_SHAPE;
     const dim3 grid((unsigned)(((long long)H * W + NB - 1) / NB), (unsigned)(blocks * n));
-    if (dtype == PH_F32)
-        hipLaunchKernelGGL((encoder_input_nhwc_kernel<float>), grid, dim3(NB), 0, (hipStream_t)stream, s, groups, n, H * W, mean, inv_std,
-                           (float *)out);
-    else
-        hipLaunchKernelGGL((encoder_input_nhwc_kernel<bf16>), grid, dim3(NB), 0, (hipStream_t)stream, s, groups, n, H * W, mean, inv_std,
-                           (bf16 *)out);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((encoder_input_nhwc_kernel<T>), grid, dim3(NB), 0, (hipStream_t)stream, s, groups, n, H * W, mean, inv_std,
+                           (T *)out);
+    });
     return check_launch();
 }

@@ -90,6 +90,27 @@ def test_decoder_glue_bf16_to_f32_head_input(F, cl):
     torch.testing.assert_close(raw.grad.float(), raw2.grad, rtol=2e-2, atol=2e-2)
 
 
+@pytest.mark.parametrize("cl", [False, True])
+def test_decoder_glue_bf16_to_f32_upsampled_with_skip(F, cl):
+    """The (bfloat16 in, float32 out) pair with the x2 upsample and a skip map: the networks use the pair only for a head's input
+    (no upsample, no skip), so its other backward instantiations -- the raw gradient through the 2 x 2 fold, the skip gradient --
+    are reached here.  Reference and tolerances of the head-input test above."""
+    g = torch.Generator().manual_seed(3)
+    raw = _leaf(torch.randn(2, 8, 3, 5, generator=g), torch.bfloat16, cl)
+    skip = _leaf(torch.randn(2, 8, 6, 10, generator=g), torch.bfloat16, cl)
+    out = F.decoder_glue(raw, skip, elu=True, upsample=True, out_dtype=torch.float32)
+    raw2, skip2 = raw.detach().float().requires_grad_(True), skip.detach().float().requires_grad_(True)
+    up = torch.nn.functional.interpolate(torch.nn.functional.elu(raw2), scale_factor=2, mode="nearest")
+    ref = torch.nn.ReflectionPad2d(1)(torch.cat((up, skip2), 1))
+    assert out.dtype == torch.float32 and out.shape == ref.shape and _layout_is(out, cl)
+    torch.testing.assert_close(out, ref, rtol=1e-6, atol=1e-6)
+    gout = torch.randn(ref.shape, generator=g).cuda()
+    out.backward(gout)
+    ref.backward(gout)
+    torch.testing.assert_close(raw.grad.float(), raw2.grad, rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(skip.grad.float(), skip2.grad, rtol=2e-2, atol=2e-2)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cl", [False, True])
 @pytest.mark.parametrize("shape", [(2, 3, 8, 10), (1, 2, 7, 9), (2, 64, 96, 320), (1, 1, 1, 1), (1, 2, 2, 3), (2, 8, 7, 9), (1, 16, 2, 3),
@@ -249,6 +270,50 @@ def test_bn_act_matches_torch(F, cfg, dtype, cl):
     close(b.grad, b2.grad, "dbeta", 1e-4 if f32 else 3e-2)
     if has_res:
         close(res.grad, res2.grad, "dres", 1e-5 if f32 else 1e-2)
+
+
+@pytest.mark.parametrize("shape,two_grads", [((2, 8, 3, 5), False), ((2, 16, 5, 7), True)])      # the second: two channel vectors a row
+def test_bn_act_nhwc_bwd_bf16_mask_from_x_equals_mask_from_y(shape, two_grads):
+    """mdx_bn_act_nhwc_bwd with y == NULL on bfloat16 maps (the ReLU mask re-derived from x): bn_act itself leaves y out only for
+    float32, so the entry point is called directly, against the same call with y given.  The input keeps every normalised value
+    more than a bfloat16 ulp of the map's largest one away from zero (checked here in float64), so both masks are the same
+    set by construction; tolerances: test_bn_act_matches_torch's for bfloat16."""
+    from mdx._lib import api, ptr, stream, workspace
+    B, Cc, H, W = shape
+    g = torch.Generator().manual_seed(5)
+    nhwc = lambda t: t.to("cuda").contiguous(memory_format=torch.channels_last)   # noqa: E731
+    sign = torch.where(torch.rand(shape, generator=g) < 0.5, -1.0, 1.0)
+    x0 = (sign * (1.0 + 0.5 * torch.rand(shape, generator=g))).to(torch.bfloat16)
+    gamma0, beta0 = 0.5 + torch.rand(Cc, generator=g), 0.1 * torch.rand(Cc, generator=g) - 0.05
+    xd = x0.double()
+    mean, var = xd.mean((0, 2, 3), keepdim=True), xd.var((0, 2, 3), unbiased=False, keepdim=True)
+    pre = (xd - mean) / torch.sqrt(var + 1e-5) * gamma0.double().view(1, -1, 1, 1) + beta0.double().view(1, -1, 1, 1)
+    assert float(pre.abs().min()) > 2.0 ** -7 * float(pre.abs().max()) and bool((pre < 0).any()) and bool((pre > 0).any())
+
+    x, gamma, beta = nhwc(x0), gamma0.cuda(), beta0.cuda()
+    dy = nhwc(torch.randn(shape, generator=g).to(torch.bfloat16))
+    dy2 = nhwc(torch.randn(shape, generator=g).to(torch.bfloat16)) if two_grads else None
+    y = torch.empty_like(x)
+    save_mean, save_invstd = torch.empty(1, Cc, device="cuda"), torch.empty(1, Cc, device="cuda")
+    nws = api.mdx_bn_nhwc_workspace_bytes(B, Cc, H, W, 1, 1)
+    ws = workspace(nws, x.device)
+    bf = torch.bfloat16
+    api.mdx_bn_act_nhwc_fwd(ptr(x, bf, cl=True), None, ptr(gamma), ptr(beta), None, None, ptr(y, bf, cl=True), ptr(save_mean),
+                            ptr(save_invstd), B, Cc, H, W, 1, 1e-5, 0.1, 1, 1, ptr(ws, torch.uint8), nws, stream())
+
+    def backward(y_or_none):
+        dx, dgamma, dbeta = torch.empty_like(x), torch.empty(Cc, device="cuda"), torch.empty(Cc, device="cuda")
+        api.mdx_bn_act_nhwc_bwd(ptr(dy, bf, cl=True), ptr(dy2, bf, optional=True, cl=True), ptr(y_or_none, bf, optional=True, cl=True),
+                                ptr(x, bf, cl=True), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), ptr(dx, bf, cl=True),
+                                None, ptr(dgamma), ptr(dbeta), B, Cc, H, W, 1, 1, 1, ptr(ws, torch.uint8), nws, stream())
+        torch.cuda.synchronize()
+        return dx, dgamma, dbeta
+    want, got = backward(y), backward(None)
+    assert bool(((y > 0) == (pre > 0).cuda()).all())                 # the mask both calls are meant to use
+    for name, a, b in zip(("dx", "dgamma", "dbeta"), got, want):
+        err = float((a.double() - b.double()).abs().max()) / (float(b.double().abs().max()) + 1e-12)
+        print(name, err)
+        assert err <= 3e-2, "%s: %g" % (name, err)
 
 
 @pytest.mark.parametrize("cl", [False, True])
