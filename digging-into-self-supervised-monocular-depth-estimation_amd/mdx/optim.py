@@ -10,7 +10,12 @@ gradient the step consumes and / or leaves parameters, moments and step counts u
 path the decision is taken on the device (three launches, capturable, no host synchronisation, deterministic; `.grad` is never
 written); `guard_stats()` is the only call that synchronises.  Where the step goes through torch's own functions -- CPU parameters,
 anything `_native_ok` rejects -- the guard does too: a float64 norm and a HOST-side skip (so that path cannot be captured), then
-`torch.nn.utils.clip_grad_norm_`, which scales `.grad` in place.  The guard's record is not part of `state_dict()`."""
+`torch.nn.utils.clip_grad_norm_`, which scales `.grad` in place.  The guard's record is not part of `state_dict()`.
+
+`WeightEMA(modules, decay)`: an exponential moving average of the weights and batch-norm statistics, updated after every optimiser
+step by csrc/ema.hip -- capturable with the step, its decay warm-up and the guard's skip decided on the device -- and exchanged with
+the live weights in place for validation and checkpoints (`swap()`, `applied()`)."""
+import contextlib
 import ctypes as C
 import struct
 
@@ -232,3 +237,191 @@ class Adam(torch.optim.Adam):
                 self._record.copy_(record)
             else:
                 self._record.zero_()             # no guarded step had run
+
+
+class _EmaTable(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("e", C.c_void_p), ("n", C.c_int64)]
+
+
+class WeightEMA(object):
+    """Shadows of every trained parameter and every float32 buffer (batch-norm running statistics; integer buffers are left alone)
+    of `modules`: after each optimiser step `update(optimizer)` moves them towards the live values,
+
+        shadow = lerp(shadow, live, 1 - d_t),   d_t = min(decay, (1 + t) / (10 + t)) with warm-up, else decay;  t = updates so far
+
+    `swap()` exchanges live and shadow storage bit for bit -- the networks, and a captured validation graph that reads the weights
+    where they live, then run on the average; a second `swap()` puts everything back -- and `applied()` does both around a block.
+    Dense float32 GPU tensors go through csrc/ema.hip (include/mdx.h: mdx_ema_update, mdx_ema_tick, mdx_ema_swap): the counters
+    are a device record, a step the optimiser's guard skipped is withheld on the device, nothing synchronises but `stats()`, and
+    the table, block maps and record are built HERE, so nothing is allocated inside a capture.  Any other tensor set (CPU,
+    another dtype, not dense) takes the same arithmetic through torch's own functions with the counters on the host.
+
+    The parameters are taken as they are at construction -- the float32 masters, never the bfloat16 copies that
+    mdx.shadow.bf16_weights shows the modules during a step -- and must keep their storage.  `shadows` (optional): {name: tensor},
+    storage of the caller's for the shadows named (a slice of one arena, say) -- shape, dtype, device and strides of the live tensor;
+    the other shadows are allocated here.  All of them start from the live values."""
+
+    native = True          # False: torch's own functions for every tensor
+
+    def __init__(self, modules, decay, warmup=True, shadows=None):
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError("decay must lie in [0, 1), got %r" % (decay,))
+        self.decay, self.warmup = decay, bool(warmup)
+        modules = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+        self.names, self.live, seen = [], [], set()
+        for i, net in enumerate(modules):
+            named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
+            named += [(n, b) for n, b in net.named_buffers() if b.dtype == torch.float32]
+            for n, t in named:
+                if id(t) not in seen:
+                    seen.add(id(t))
+                    self.names.append("%d.%s" % (i, n))
+                    self.live.append(t)
+        if not self.live:
+            raise ValueError("WeightEMA: the modules have no trained parameter and no float32 buffer")
+        with torch.no_grad():
+            given = dict(shadows or {})
+            self.shadow = [given.pop(n) if n in given else torch.empty_like(t)      # preserve_format: channels-last keeps its strides
+                           for n, t in zip(self.names, self.live)]
+            if given:
+                raise KeyError("WeightEMA: no parameter or float32 buffer is called %s" % ", ".join(sorted(given)))
+            for n, e, t in zip(self.names, self.shadow, self.live):
+                if (e.shape, e.dtype, e.device, e.stride()) != (t.shape, t.dtype, t.device, t.stride()) or e is t:
+                    raise ValueError("WeightEMA: the shadow given for %s does not match its tensor" % n)
+            for e, t in zip(self.shadow, self.live):
+                e.copy_(t)
+        self._host = dict(updates=0, held=0)
+        self._native = self._native_ok()
+        self._record = self._table = self._launches = None
+        if self._native:
+            dev = self.live[0].device
+            assert C.sizeof(_EmaTable) == api.mdx_ema_table_entry_bytes() and api.mdx_ema_record_bytes() == 16
+            host = (_EmaTable * len(self.live))()
+            for i, (t, e) in enumerate(zip(self.live, self.shadow)):
+                host[i] = _EmaTable(t.data_ptr(), e.data_ptr(), t.numel())
+            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
+            self._launches = Adam._launches(self.live, 0)
+            self._record = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._key = tuple(t.data_ptr() for t in self.live)
+
+    def _native_ok(self):
+        if not self.native:
+            return False
+        dev = self.live[0].device
+        for t, e in zip(self.live, self.shadow):
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.numel() > 0
+                    and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) and Adam._dense(e, t)):
+                return False
+        return True
+
+    def _check_native(self):
+        dev = self.live[0].device
+        if dev.index != torch.cuda.current_device():
+            raise _lib.MdxError("mdx.optim.WeightEMA: tensors live on %s but the current device is cuda:%d"
+                                % (dev, torch.cuda.current_device()))
+        if tuple(t.data_ptr() for t in self.live) != self._key:
+            raise _lib.MdxError("mdx.optim.WeightEMA: a parameter or buffer has changed its storage since construction")
+
+    def _weight(self, t):
+        d = min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+        return float(torch.tensor(1.0 - d, dtype=torch.float64).float())
+
+    @torch.no_grad()
+    def update(self, optimizer=None):
+        """One update, after `optimizer.step()`.  A guarded mdx.optim.Adam hands its device record over when its last step took the
+        native path; where the guard decided on the host (torch's own step), so does the skip here."""
+        guard = None
+        if optimizer is not None and getattr(optimizer, "guarded", False):
+            if not optimizer._last_native:
+                if optimizer._host_stats["skipped"]:
+                    self._host["held"] += 1
+                    return
+            elif optimizer._record is not None:
+                if self._native and optimizer._record.device == self.live[0].device:
+                    guard = optimizer._record.data_ptr()
+                elif optimizer.guard_stats()["skipped"]:              # torch-path average of a native optimiser: read it
+                    self._host["held"] += 1
+                    return
+        if not self._native:
+            w = self._weight(self._host["updates"])
+            for e, t in zip(self.shadow, self.live):
+                e.lerp_(t.detach(), w)
+            self._host["updates"] += 1
+            return
+        self._check_native()
+        table, record = self._table.data_ptr(), self._record.data_ptr()
+        for first, count, blockmap, nblocks in self._launches:
+            api.mdx_ema_update(table, first, count, blockmap.data_ptr(), nblocks, self.decay, int(self.warmup), record, guard, stream())
+        api.mdx_ema_tick(record, guard, stream())
+
+    @torch.no_grad()
+    def swap(self):
+        """Exchange live and shadow values in place, bit for bit.  Two swaps are the identity."""
+        if not self._native:
+            for e, t in zip(self.shadow, self.live):
+                keep = e.clone()
+                e.copy_(t)
+                t.copy_(keep)
+            return
+        self._check_native()
+        for first, count, blockmap, nblocks in self._launches:
+            api.mdx_ema_swap(self._table.data_ptr(), first, count, blockmap.data_ptr(), nblocks, stream())
+
+    @contextlib.contextmanager
+    def applied(self):
+        """While the block runs, the modules hold the average (and the shadows the live values); put back on the way out, also
+        when the block raises."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def stats(self):
+        """{updates, held}.  Reads the device record: the one call that synchronises."""
+        out = dict(self._host)
+        if self._record is not None:
+            updates, held = self._record.cpu().tolist()
+            out["updates"] += updates
+            out["held"] += held
+        return out
+
+    def _set_counters(self, updates, held):
+        if self._record is not None:
+            self._record.copy_(torch.tensor([int(updates), int(held)], dtype=torch.int64))
+            self._host = dict(updates=0, held=0)
+        else:
+            self._host = dict(updates=int(updates), held=int(held))
+
+    def state_dict(self):
+        st = self.stats()
+        return {"shadow": {n: e.detach().clone() for n, e in zip(self.names, self.shadow)}, "updates": st["updates"], "held": st["held"]}
+
+    @torch.no_grad()
+    def load_state_dict(self, state):
+        missing = [n for n in self.names if n not in state["shadow"]]
+        if missing:
+            raise KeyError("WeightEMA.load_state_dict: no shadow for %s" % ", ".join(missing[:5]))
+        for n, e in zip(self.names, self.shadow):
+            e.copy_(state["shadow"][n])
+        self._set_counters(state["updates"], state["held"])
+
+    @torch.no_grad()
+    def reset(self):
+        """Start again from the live values: shadows equal to them, no update counted."""
+        for e, t in zip(self.shadow, self.live):
+            e.copy_(t)
+        self._set_counters(0, 0)
+
+    def snapshot(self):
+        """Shadows and counters, for a caller that undoes steps (model_train.graphed_step's warm-up)."""
+        return ([e.detach().clone() for e in self.shadow], None if self._record is None else self._record.clone(), dict(self._host))
+
+    @torch.no_grad()
+    def restore(self, snapshot):
+        for e, s in zip(self.shadow, snapshot[0]):
+            e.copy_(s)
+        if self._record is not None:
+            self._record.copy_(snapshot[1])
+        self._host = dict(snapshot[2])

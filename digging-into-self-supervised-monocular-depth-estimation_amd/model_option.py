@@ -65,6 +65,14 @@ def options(argv=None):
     p.add_argument("--skip_nonfinite", type=int, default=0,
                    help="1: a step whose global gradient norm is not finite changes no weight, moment or step count (decided on the "
                         "device; counted, printed after each epoch)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the weights and batch-norm statistics with this decay, e.g. 0.999, updated "
+                        "on the device after every optimiser step (mdx/optim.py: WeightEMA, csrc/ema.hip; capturable); 0: off.  Trainer only: model_test.py always evaluates the live encoder<N>.pt / "
+                        "decoder<N>.pt; model_ema_eval.py evaluates the averaged ema_<key><N>.pt with this option set")
+    p.add_argument("--ema_warmup", type=int, default=1,
+                   help="with --ema_decay: update t uses min(decay, (1 + t) / (10 + t)), so the early average follows the weights")
+    p.add_argument("--ema_valid", type=int, default=1,
+                   help="with --ema_decay: each epoch's validation runs on the averaged weights (exchanged in place and put back)")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

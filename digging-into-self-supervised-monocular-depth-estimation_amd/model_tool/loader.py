@@ -167,6 +167,11 @@ class setting(object):
             fused = str(self.device).startswith("cuda")
             self.optim["optimizer"] = torch.optim.Adam(self.parameters, float(self.opt.learning_rate), fused=fused)
         self.optim["scheduler"] = torch.optim.lr_scheduler.StepLR(self.optim["optimizer"], self.opt.scheduler_step)
+        # --ema_decay (off by default): an average of the weights and batch-norm statistics, updated after every optimiser step
+        decay = float(_opt(self.opt, "ema_decay", 0.0) or 0.0)
+        if decay > 0:
+            from mdx.optim import WeightEMA
+            self.optim["ema"] = WeightEMA(self.raw_model.values(), decay, warmup=bool(_opt(self.opt, "ema_warmup", 1)))
 
     def set_train(self):
         for value in self.model.values():

@@ -77,11 +77,18 @@ class control(object):
         loss_directory = os.path.join(save_directory, "loss")
         os.makedirs(loss_directory, exist_ok=True)
         models = getattr(setting, "raw_model", setting.model)
+        ema = setting.optim.get("ema")
         if (epoch + 1) % 2 == 0 or (epoch + 1) == self.opt.epoch:
             for key in models:
                 torch.save(models[key].state_dict(), os.path.join(save_directory, key + str(epoch + 1) + ".pt"))
+            if ema is not None:
+                # the averaged networks under the live files' keys (model_test.load_weights reads them as they are)
+                with ema.applied():
+                    for key in models:
+                        torch.save(models[key].state_dict(), os.path.join(save_directory, "ema_" + key + str(epoch + 1) + ".pt"))
             # what a restart needs beyond the reference's files (it saves weights only, logger.py:51-68)
-            torch.save({"epoch": epoch + 1, "optimizer": setting.optim["optimizer"].state_dict(),
+            extra = {"ema": ema.state_dict()} if ema is not None else {}
+            torch.save({"epoch": epoch + 1, "optimizer": setting.optim["optimizer"].state_dict(), **extra,
                         "scheduler": setting.optim["scheduler"].state_dict(),
                         # steps served by the in-kernel noise generator (compute.noise_rng): a resumed run goes on in the
                         # stream instead of replaying the draws of epoch 0
@@ -110,6 +117,15 @@ class control(object):
         state = torch.load(os.path.join(save_directory, "state" + str(epoch) + ".pt"), map_location=self.device)
         setting.optim["optimizer"].load_state_dict(state["optimizer"])
         setting.optim["scheduler"].load_state_dict(state["scheduler"])
+        ema = setting.optim.get("ema")
+        if ema is not None:
+            if state.get("ema") is not None:
+                ema.load_state_dict(state["ema"])
+            else:
+                ema.reset()
+                if int(os.environ.get("RANK", "0")) == 0:
+                    print("resume: state%d.pt holds no weight EMA; the average starts from the loaded weights with 0 updates"
+                          % epoch, flush=True)
         if compute is not None and state.get("noise_offset") is not None:
             compute.set_noise_offset(state["noise_offset"])
         for mine, key in ((train_log, "train_log"), (valid_log, "valid_log")):

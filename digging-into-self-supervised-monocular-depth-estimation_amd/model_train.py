@@ -3,6 +3,7 @@
     python model_train.py --dataset synthetic --epoch 1
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 model_train.py ...
 """
+import contextlib
 import os
 import sys
 
@@ -101,7 +102,11 @@ class graphed_step(object):
 
     The step guard (--clip_grad_norm, --skip_nonfinite) is part of optimizer.step(): it runs after the gradient exchange, on the
     exchanged gradients, so every rank sees the same bits and takes the same decision; in the split form it is part of graph B.
-    Its totals are put back after the warm-up with the moments and step counters."""
+    Its totals are put back after the warm-up with the moments and step counters.
+
+    The weight average (--ema_decay) is updated directly after optimizer.step(), inside the same graph (graph B in the split form);
+    its shadows and counters are put back after the warm-up too, so the first replay is update 0 from shadows equal to the
+    initial weights."""
 
     def __init__(self, tr, example, warmup=3):
         self.tr = tr
@@ -134,6 +139,8 @@ class graphed_step(object):
         had_state = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                      for p, st in opt.state.items()}
         saved_guard = opt.guard_snapshot() if getattr(opt, "guarded", False) else None     # the step guard's totals (mdx/optim.py)
+        ema = tr.setting.optim.get("ema")          # the weight average (mdx/optim.py: WeightEMA): the warm-up's updates are undone
+        saved_ema = ema.snapshot() if ema is not None else None
         # ONE side stream for the warm-up and the capture: the gradient-accumulation nodes autograd creates during
         # the captured forward then live on the stream that produces their gradients
         self.stream = torch.cuda.Stream(dev)
@@ -156,6 +163,8 @@ class graphed_step(object):
                     rng.tensor.copy_(saved_rng)
                 if saved_guard is not None:
                     opt.guard_restore(saved_guard)
+                if saved_ema is not None:
+                    ema.restore(saved_ema)
             for m, n in zip(self.bns, saved_bn):
                 m._pending_batches = n
         torch.cuda.current_stream(dev).wait_stream(self.stream)
@@ -172,7 +181,7 @@ class graphed_step(object):
                 outputs = tr._step_gradients(dict(self.static))
             self.graph_apply = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_apply, stream=self.stream, capture_error_mode="thread_local", pool=self.graph.pool()):
-                tr.setting.optim["optimizer"].step()
+                tr._apply_step()
         else:
             with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
                 outputs = tr._eager_step(dict(self.static))
@@ -349,8 +358,16 @@ class trainer(object):
         outputs["loss"].backward()
         if sync is not None:
             sync.finish()
-        self.setting.optim["optimizer"].step()
+        self._apply_step()
         return outputs
+
+    def _apply_step(self):
+        """Adam, then the weight average's update (--ema_decay), which reads the guard's decision where the optimiser left it."""
+        optimizer = self.setting.optim["optimizer"]
+        optimizer.step()
+        ema = self.setting.optim.get("ema")
+        if ema is not None:
+            ema.update(optimizer)
 
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
@@ -416,12 +433,16 @@ class trainer(object):
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
-            for step, valid_inputs in enumerate(self.batches(self.setting.valid_dataloader)):
-                with torch.no_grad():
-                    valid_outputs = self.valid_step(valid_inputs)
-                    batch_valid = self.control.metric(valid_inputs, valid_outputs, batch_valid)
-                if self.opt.max_steps and step + 1 >= self.opt.max_steps:
-                    break
+            # --ema_valid: the validation reads the averaged weights -- exchanged in place by eager launches outside the validation
+            # graph, which reads the weights where they live -- and the live ones are back before the next training step
+            ema = self.setting.optim.get("ema")
+            with ema.applied() if ema is not None and getattr(self.opt, "ema_valid", 1) else contextlib.nullcontext():
+                for step, valid_inputs in enumerate(self.batches(self.setting.valid_dataloader)):
+                    with torch.no_grad():
+                        valid_outputs = self.valid_step(valid_inputs)
+                        batch_valid = self.control.metric(valid_inputs, valid_outputs, batch_valid)
+                    if self.opt.max_steps and step + 1 >= self.opt.max_steps:
+                        break
             self.setting.optim["scheduler"].step()
             if self._graphed is not None:         # StepLR wrote a new Python value: hand it to the captured Adam's lr tensor
                 lr = self.setting.optim["scheduler"].get_last_lr()[0]
@@ -440,6 +461,9 @@ class trainer(object):
                     g = optimizer.guard_stats()
                     print("step guard: %d steps, %d skipped, last gradient norm %g" % (g["steps"], g["skipped_steps"], g["total_norm"]),
                           flush=True)
+                if ema is not None:
+                    e = ema.stats()
+                    print("weight EMA: %d updates, %d held" % (e["updates"], e["held"]), flush=True)
             self.control.save(epoch, epoch_train, epoch_valid, self.setting, compute=self.compute)
 
 

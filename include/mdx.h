@@ -270,6 +270,26 @@ int mdx_adam_guard_finish(const void *table, int ntensors, const double *partial
 int mdx_adam_step_guarded(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
                           const float *lr_ptr, double lr, double beta1, double beta2, double eps, const void *record, void *stream);
 
+/* An exponential moving average of the weights, kept on the device (csrc/ema.hip; mdx.optim.WeightEMA): capturable with the step,
+ * its decay warm-up and the guard's skip decided from device records.  table: DEVICE array of { float *live, *shadow; int64_t numel }
+ * (mdx_ema_table_entry_bytes() each; the shadow has the live tensor's dense storage order); first / count / blockmap / nblocks as
+ * for mdx_adam_step (count <= mdx_adam_max_tensors(), chunks of mdx_adam_chunk() elements).  record: DEVICE
+ * { int64 updates; int64 held } (mdx_ema_record_bytes(), 8-byte aligned, zeroed once by the caller).
+ *   mdx_ema_update  t = record.updates; d = warmup ? min(decay, (1 + t) / (10 + t)) : decay, in double; w = (float)(1 - d);
+ *                   shadow = lerp(shadow, live, w) by ATen's rule in float32: w < 0.5 ? e + w * (p - e) : p - (p - e) * (1 - w).
+ *                   The record is only read: several calls of one update (more than mdx_adam_max_tensors() tensors) see the same t.
+ *                   guard_record: NULL, or the step guard's record (mdx_adam_guard_finish); when it says skipped, nothing is written.
+ *   mdx_ema_tick    one thread, after the last mdx_ema_update of an update: updates += 1, or held += 1 when the guard record
+ *                   says skipped.
+ *   mdx_ema_swap    exchanges live and shadow bit for bit, in place; two calls are the identity.
+ * A decay that is NaN or outside [0, 1) is MDX_ERR_BAD_SHAPE. */
+size_t mdx_ema_table_entry_bytes(void);
+size_t mdx_ema_record_bytes(void);
+int mdx_ema_update(const void *table, int first, int count, const void *blockmap, int nblocks, double decay, int warmup,
+                   const void *record, const void *guard_record, void *stream);
+int mdx_ema_tick(void *record, const void *guard_record, void *stream);
+int mdx_ema_swap(const void *table, int first, int count, const void *blockmap, int nblocks, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fine-grained ops behind the reference's model_layer / model_loss API (each differentiable)
  * ---------------------------------------------------------------------------------------- */
