@@ -14,7 +14,10 @@ anything `_native_ok` rejects -- the guard does too: a float64 norm and a HOST-s
 
 `WeightEMA(modules, decay)`: an exponential moving average of the weights and batch-norm statistics, updated after every optimiser
 step by csrc/ema.hip -- capturable with the step, its decay warm-up and the guard's skip decided on the device -- and exchanged with
-the live weights in place for validation and checkpoints (`swap()`, `applied()`)."""
+the live weights in place for validation and checkpoints (`swap()`, `applied()`).
+
+`WeightDigest(tensors, names)`: one 64-bit digest per tensor by csrc/digest.hip -- a read-only pass, an integer sum without order or
+tolerance -- for the replica check of a data-parallel run and the checkpoint verification of a resumed one."""
 import contextlib
 import ctypes as C
 import struct
@@ -425,3 +428,115 @@ class WeightEMA(object):
         if self._record is not None:
             self._record.copy_(snapshot[1])
         self._host = dict(snapshot[2])
+
+
+class _DigestTable(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("n", C.c_int64)]
+
+
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class WeightDigest(object):
+    """One 64-bit digest per tensor of `tensors`, for equality only: what data-parallel ranks compare after a step
+    (model_tool.parallel.check_replicas) and what a checkpoint's state file records of the weight files beside it
+    (model_tool.logger.control).  The digest of a tensor is the sum modulo 2^64, over storage index i = 0 .. numel - 1 of its dense
+    storage, of a 32-bit hash of (i, the 32-bit word at i) -- include/mdx.h states the recipe.  The words are never read as
+    floats (NaN payloads and the sign of zero count), the sum has no order and no tolerance, and a tensor is hashed in STORAGE
+    order: a channels-last tensor and its contiguous copy have different digests.
+
+    Dense float32 GPU tensors on one device, contiguous or channels-last, go through csrc/digest.hip (mdx_digest_words): the table,
+    block maps and the int64 output tensor are built HERE, nothing is allocated later, `compute()` launches without synchronising
+    and is capturable; `host()` is the one call that synchronises.  Any other set of dense float32 tensors (CPU tensors, or
+    `native = False`) is hashed with numpy over the storage.  The tensors must keep their storage.  `names` default to "0", "1", ..."""
+
+    native = True          # False: numpy for every tensor
+
+    def __init__(self, tensors, names=None):
+        if _capturing():
+            raise _lib.MdxError("mdx.optim.WeightDigest: built while the current stream is being captured")
+        self.tensors = [t.detach() for t in tensors]
+        self.names = [str(i) for i in range(len(self.tensors))] if names is None else [str(n) for n in names]
+        if not self.tensors:
+            raise ValueError("WeightDigest: no tensors")
+        if len(self.names) != len(self.tensors) or len(set(self.names)) != len(self.names):
+            raise ValueError("WeightDigest: %d tensors need %d distinct names" % (len(self.tensors), len(self.tensors)))
+        for n, t in zip(self.names, self.tensors):
+            if t.dtype != torch.float32 or not self._dense(t):
+                raise ValueError("WeightDigest: %s is %s with shape %s and strides %s; dense float32 storage is hashed"
+                                 % (n, t.dtype, tuple(t.shape), t.stride()))
+        self._native = self._native_ok()
+        self._table = self._launches = None
+        if self._native:
+            dev = self.tensors[0].device
+            assert C.sizeof(_DigestTable) == api.mdx_digest_table_entry_bytes()
+            host = (_DigestTable * len(self.tensors))()
+            for i, t in enumerate(self.tensors):
+                host[i] = _DigestTable(t.data_ptr(), t.numel())
+            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
+            self._launches = Adam._launches(self.tensors, 0)
+            self._out = torch.zeros(len(self.tensors), dtype=torch.int64, device=dev)
+            self._key = tuple(t.data_ptr() for t in self.tensors)
+        else:
+            self._out = torch.zeros(len(self.tensors), dtype=torch.int64)
+
+    @staticmethod
+    def _dense(t):
+        """Non-overlapping and without gaps: the strides are a permutation of the contiguous ones."""
+        expect = 1
+        for st, sz in sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz != 1):
+            if st != expect:
+                return False
+            expect *= sz
+        return True
+
+    def _native_ok(self):
+        if not self.native:
+            return False
+        dev = self.tensors[0].device
+        return all(t.is_cuda and t.device == dev and t.numel() > 0
+                   and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) for t in self.tensors)
+
+    def _check_native(self):
+        dev = self.tensors[0].device
+        if dev.index != torch.cuda.current_device():
+            raise _lib.MdxError("mdx.optim.WeightDigest: tensors live on %s but the current device is cuda:%d"
+                                % (dev, torch.cuda.current_device()))
+        if tuple(t.data_ptr() for t in self.tensors) != self._key:
+            raise _lib.MdxError("mdx.optim.WeightDigest: a tensor has changed its storage since construction")
+
+    @staticmethod
+    def _numpy_digest(t):
+        """The recipe of include/mdx.h over the storage of one dense float32 tensor, as a signed 64-bit integer."""
+        import numpy as np
+        n = t.numel()
+        words = torch.as_strided(t, (n,), (1,)).cpu().contiguous().view(torch.int32).numpy().view(np.uint32)
+        k = words ^ (np.arange(n, dtype=np.uint64).astype(np.uint32) * np.uint32(0x9E3779B1))
+        k ^= k >> np.uint32(16)
+        k *= np.uint32(0x85EBCA6B)
+        k ^= k >> np.uint32(13)
+        k *= np.uint32(0xC2B2AE35)
+        k ^= k >> np.uint32(16)
+        total = int(k.sum(dtype=np.uint64))                 # numpy's unsigned sum wraps, as the kernel's does
+        return total - (1 << 64) if total >> 63 else total
+
+    @torch.no_grad()
+    def compute(self):
+        """-> the int64 tensor of the digests (the 64 bits of each sum; the same tensor at every call), on the tensors' device
+        without a synchronisation on the native path, on the host otherwise."""
+        if not self._native:
+            if _capturing() and any(t.is_cuda for t in self.tensors):
+                raise _lib.MdxError("mdx.optim.WeightDigest: the numpy path reads the tensors on the host and cannot be captured")
+            self._out.copy_(torch.tensor([self._numpy_digest(t) for t in self.tensors], dtype=torch.int64))
+            return self._out
+        self._check_native()
+        for first, count, blockmap, nblocks in self._launches:
+            api.mdx_digest_words(self._table.data_ptr(), first, count, blockmap.data_ptr(), nblocks, self._out.data_ptr(), stream())
+        return self._out
+
+    def host(self):
+        """{name: digest as an integer in [0, 2^64)}: computes, then reads -- the one call that synchronises."""
+        if _capturing():
+            raise _lib.MdxError("mdx.optim.WeightDigest.host() synchronises and the current stream is being captured")
+        return {n: int(d) & 0xFFFFFFFFFFFFFFFF for n, d in zip(self.names, self.compute().cpu().tolist())}

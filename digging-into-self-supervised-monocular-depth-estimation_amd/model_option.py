@@ -73,6 +73,11 @@ def options(argv=None):
                    help="with --ema_decay: update t uses min(decay, (1 + t) / (10 + t)), so the early average follows the weights")
     p.add_argument("--ema_valid", type=int, default=1,
                    help="with --ema_decay: each epoch's validation runs on the averaged weights (exchanged in place and put back)")
+    p.add_argument("--check_weights", type=int, default=0,
+                   help="N > 0: before the first step, after every N-th step and before each checkpoint, digest the float32 master "
+                        "weights on the device (mdx/optim.py: WeightDigest, csrc/digest.hip) and, in a data-parallel run, compare the "
+                        "digests across the ranks (one int64 all-reduce; a difference raises on every rank); state<N>.pt records the "
+                        "digests and --resume verifies the weight files against them; 0: off")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

@@ -172,6 +172,12 @@ class setting(object):
         if decay > 0:
             from mdx.optim import WeightEMA
             self.optim["ema"] = WeightEMA(self.raw_model.values(), decay, warmup=bool(_opt(self.opt, "ema_warmup", 1)))
+        # --check_weights (off by default): digests of the trained float32 master parameters, for the replica check and the
+        # checkpoint verification.  Batch-norm statistics are per rank by design (set_model) and are left out.
+        if int(_opt(self.opt, "check_weights", 0) or 0) > 0:
+            from mdx.optim import WeightDigest
+            name = {id(p): "%s.%s" % (key, n) for key, m in self.raw_model.items() for n, p in m.named_parameters()}
+            self.optim["digest"] = WeightDigest(self.parameters, [name[id(p)] for p in self.parameters])
 
     def set_train(self):
         for value in self.model.values():

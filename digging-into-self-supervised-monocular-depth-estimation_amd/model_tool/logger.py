@@ -88,6 +88,12 @@ class control(object):
                         torch.save(models[key].state_dict(), os.path.join(save_directory, "ema_" + key + str(epoch + 1) + ".pt"))
             # what a restart needs beyond the reference's files (it saves weights only, logger.py:51-68)
             extra = {"ema": ema.state_dict()} if ema is not None else {}
+            digest = setting.optim.get("digest")
+            if digest is not None:
+                # --check_weights: the digests of the live weights just written, each with the strides it was taken over (a
+                # digest follows the storage order), so that `resume` can tell the weight files are the ones written here
+                now = digest.host()
+                extra["weights_digest"] = {n: [now[n], list(t.stride())] for n, t in zip(digest.names, digest.tensors)}
             torch.save({"epoch": epoch + 1, "optimizer": setting.optim["optimizer"].state_dict(), **extra,
                         "scheduler": setting.optim["scheduler"].state_dict(),
                         # steps served by the in-kernel noise generator (compute.noise_rng): a resumed run goes on in the
@@ -100,6 +106,36 @@ class control(object):
             for key in self.metric_name:
                 np.save(os.path.join(loss_directory, key + ".npy"), np.asarray(valid_log[key]))
                 np.save(os.path.join(loss_directory, "train_" + key + ".npy"), np.asarray(train_log[key]))
+
+    @staticmethod
+    def _verify_weights(digest, recorded, epoch):
+        """--check_weights on a resume: the digests of the weights just loaded against the ones state<epoch>.pt recorded.  A digest
+        follows the storage order, so a tensor whose strides (over its dimensions larger than 1) are not the recorded ones --
+        another --channels_last plan -- is reported as not comparable and passes."""
+        if digest is None:
+            return
+        tell = int(os.environ.get("RANK", "0")) == 0
+        if recorded is None:
+            if tell:
+                print("resume: state%d.pt records no weight digests (written without --check_weights); the weight files are not "
+                      "verified" % epoch, flush=True)
+            return
+        now, differ, apart = digest.host(), [], []
+        for n, t in zip(digest.names, digest.tensors):
+            strides = [st for st, sz in zip(t.stride(), t.shape) if sz != 1]
+            if n not in recorded or [st for st, sz in zip(recorded[n][1], t.shape) if sz != 1] != strides:
+                apart.append(n)
+            elif int(recorded[n][0]) != now[n]:
+                differ.append(n)
+        if apart and tell:
+            print("resume: %d of %d tensors are laid out differently from the run that wrote state%d.pt (%s%s); their digests are "
+                  "not comparable" % (len(apart), len(now), epoch, ", ".join(apart[:5]), ", ..." if len(apart) > 5 else ""), flush=True)
+        if differ:
+            raise RuntimeError("cannot resume from epoch %d: the weight files are not the ones state%d.pt was written beside -- the "
+                               "digest differs in %d of %d tensors: %s%s" % (epoch, epoch, len(differ), len(now), ", ".join(differ[:5]),
+                                                                             ", ..." if len(differ) > 5 else ""))
+        if tell:
+            print("resume: weight digests of %d tensors agree with state%d.pt" % (len(now) - len(apart), epoch), flush=True)
 
     def resume(self, setting, epoch, train_log=None, valid_log=None, compute=None):
         """Restart from the files `save` wrote after `epoch` epochs (every rank loads them): network weights from the
@@ -115,6 +151,7 @@ class control(object):
                                         "epochs and after the last one)" % (epoch, path))
             models[key].load_state_dict(torch.load(path, map_location=self.device))
         state = torch.load(os.path.join(save_directory, "state" + str(epoch) + ".pt"), map_location=self.device)
+        self._verify_weights(setting.optim.get("digest"), state.get("weights_digest"), epoch)
         setting.optim["optimizer"].load_state_dict(state["optimizer"])
         setting.optim["scheduler"].load_state_dict(state["scheduler"])
         ema = setting.optim.get("ema")

@@ -276,6 +276,38 @@ def broadcast_state(modules, src=0, group=None):
                 dist.broadcast(t, src, group=group)
 
 
+class ReplicaMismatch(RuntimeError):
+    """The ranks of a data-parallel run no longer hold the same weights."""
+
+
+def check_replicas(digest, group=None):
+    """Do all ranks hold the same weights?  `digest`: an mdx.optim.WeightDigest over the tensors that must agree (the trainer's:
+    the float32 master parameters; batch-norm statistics are per rank by design and left out).  Computes the digests where the
+    tensors live, then ONE all_reduce(MAX) over the int64 vector [d, ~d] -- `~` reverses the signed order, so ~max(~d) is the
+    minimum -- and one host read.  Where min != max it raises ReplicaMismatch naming up to five tensors; every rank sees the same
+    reduced vector, so every rank raises.  Without a process group it only computes.  -> the number of tensors compared.
+
+    broadcast_state makes the ranks equal ONCE; after that only this looks: a gradient view that missed the exchange, a guard
+    decision that differed between ranks or a resume that read another file diverge silently.  A synchronous collective: eager,
+    between the replays of a captured step, never inside a capture."""
+    _refuse_under_capture("check_replicas")
+    d = digest.compute()
+    if not (dist.is_available() and dist.is_initialized()):
+        return len(digest.names)
+    n = d.numel()
+    both = torch.cat([d, ~d])
+    if dist.get_backend(group) != "nccl":
+        both = both.cpu()
+    dist.all_reduce(both, op=dist.ReduceOp.MAX, group=group)
+    both = both.cpu()
+    hi, lo = both[:n], ~both[n:]
+    bad = torch.nonzero(hi != lo).flatten().tolist()
+    if bad:
+        raise ReplicaMismatch("the weights differ between the %d ranks in %d of %d tensors: %s%s" % (
+            dist.get_world_size(group), len(bad), n, ", ".join(digest.names[i] for i in bad[:5]), ", ..." if len(bad) > 5 else ""))
+    return n
+
+
 def mean_over_ranks(values, device, group=None):
     """Scalars (one per metric) averaged over the job: one all-reduce of len(values) numbers."""
     if dist.is_available() and dist.is_initialized():

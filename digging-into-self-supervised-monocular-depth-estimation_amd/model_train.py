@@ -369,6 +369,18 @@ class trainer(object):
         if ema is not None:
             ema.update(optimizer)
 
+    _weight_checks = 0
+
+    def check_weights(self):
+        """--check_weights: digest the float32 master weights where they live and compare the digests across the ranks
+        (model_tool/parallel.py: check_replicas; raises ReplicaMismatch on every rank).  Eager launches on the current stream -- the
+        one the step ran on or was replayed on -- between the replays of a captured step, never inside a graph."""
+        digest = self.setting.optim.get("digest")
+        if digest is not None:
+            from model_tool.parallel import check_replicas
+            check_replicas(digest)
+            self._weight_checks += 1
+
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
         (--noise cpu: torch.randn on the CPU + a copy from pageable memory), not with a non-RCCL process group.  With more than
@@ -420,6 +432,10 @@ class trainer(object):
         start = 0
         if getattr(self.opt, "resume", 0):     # weights, optimiser, scheduler and the per-epoch logs so far
             start = self.control.resume(self.setting, self.opt.resume, epoch_train, epoch_valid, compute=self.compute)
+        # --check_weights N: the ranks' weights are compared before the first step (behind broadcast_state or resume), after every
+        # N-th step of the run and before each checkpoint
+        every, done = int(getattr(self.opt, "check_weights", 0) or 0), 0
+        self.check_weights()
         for epoch in range(start, self.opt.epoch):
             batch_train = {k: [] for k in names}
             batch_valid = {k: [] for k in names}
@@ -430,6 +446,9 @@ class trainer(object):
             for step, train_inputs in enumerate(self.batches(self.setting.train_dataloader)):
                 train_outputs = self.train_step(train_inputs)
                 batch_train = self.control.metric(train_inputs, train_outputs, batch_train)
+                done += 1
+                if every > 0 and done % every == 0:
+                    self.check_weights()
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
@@ -464,6 +483,9 @@ class trainer(object):
                 if ema is not None:
                     e = ema.stats()
                     print("weight EMA: %d updates, %d held" % (e["updates"], e["held"]), flush=True)
+                if every > 0:
+                    print("weight check: %d checks, ranks agree" % self._weight_checks, flush=True)
+            self.check_weights()
             self.control.save(epoch, epoch_train, epoch_valid, self.setting, compute=self.compute)
 
 

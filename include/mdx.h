@@ -290,6 +290,24 @@ int mdx_ema_update(const void *table, int first, int count, const void *blockmap
 int mdx_ema_tick(void *record, const void *guard_record, void *stream);
 int mdx_ema_swap(const void *table, int first, int count, const void *blockmap, int nblocks, void *stream);
 
+/* A 64-bit digest of every weight tensor, computed on the device (csrc/digest.hip; mdx.optim.WeightDigest): what data-parallel ranks
+ * compare after a step (model_tool/parallel.py: check_replicas) and what a checkpoint's state file records of the weight files
+ * beside it.  table: DEVICE array of { const uint32_t *words; int64_t numel } (mdx_digest_table_entry_bytes() = 16 each; the tensor's
+ * dense storage, read as 32-bit words); first / count / blockmap / nblocks as for mdx_adam_step (count <= mdx_adam_max_tensors(),
+ * chunks of mdx_adam_chunk() words).  out: DEVICE array of at least first + count 64-bit words, 8-byte aligned.
+ *   mdx_digest_words  out[first + t] = the digest of table entry first + t, t = 0 .. count - 1: the sum modulo 2^64, over storage
+ *                     index i = 0 .. numel - 1, of the 32-bit hash of (i, u = word i):
+ *                         k = u ^ ((uint32_t)i * 0x9E3779B1u);
+ *                         k ^= k >> 16;  k *= 0x85EBCA6Bu;  k ^= k >> 13;  k *= 0xC2B2AE35u;  k ^= k >> 16;
+ *                     The words are never read as floats: NaN payloads and the sign of zero count, an all-zero tensor has a
+ *                     non-zero digest, two exchanged elements change it.  An integer sum: any order of the blocks gives the same
+ *                     bits, there is no tolerance.  The call clears out[first .. first + count - 1] itself (a small launch
+ *                     on `stream` in front of the pass): callers never zero, and the pair is capturable and replayable.
+ * The index is taken modulo 2^32: a tensor of 2^32 words or more is not refused; its words 2^32 apart share their index.
+ * A misaligned out is MDX_ERR_MISALIGNED. */
+size_t mdx_digest_table_entry_bytes(void);
+int mdx_digest_words(const void *table, int first, int count, const void *blockmap, int nblocks, uint64_t *out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fine-grained ops behind the reference's model_layer / model_loss API (each differentiable)
  * ---------------------------------------------------------------------------------------- */
