@@ -1,11 +1,16 @@
 """GPU: the bits mdx.optim.Adam and mdx.optim.WeightEMA leave behind, against literals recorded on the build of commit 3b915bb (per-group
-tables for the plain step, one table for the guarded one, the average's own; LABNOTES.md, "Optimiser and EMA: one plan").  They are
+tables for the plain step, one table for the guarded one, the average's own; LABNOTES.md, "Optimiser, EMA and digest: one header").  They are
 the yardstick for any rearrangement of the plans, tables and launches that is meant to change no number: the tolerance tests
 (tests/test_gpu_optim.py, test_gpu_guard.py, test_gpu_ema.py) would pass a table offset that landed on a similar tensor; a digest
 does not.  Neither kernel file uses atomics, the reductions add in a fixed order: the bits are reproducible (two runs in one
 process and two processes gave the same digests).
 
-The set holds the smallest shapes at which the work split (4096 elements per block, 384 tensors per launch) can go wrong."""
+The set holds the smallest shapes at which the work split (4096 elements per block, 384 tensors per launch) can go wrong.
+
+The second half holds the same runs to what a graph capture would see of them -- which entry points are called with which slice of
+which plan, and how many allocations each step makes -- against literals recorded by this file's code on the build of commit
+73278bc (LABNOTES.md, same section: the second attempt).  A rearrangement that is meant to leave a captured step alone has to meet
+both halves."""
 import hashlib
 import importlib
 
@@ -46,9 +51,14 @@ class _Holder(torch.nn.Module):
         self.register_buffer("running", torch.linspace(-1.0, 1.0, 37, device="cuda"))
 
 
-def _run(variant):
+def _allocations():
+    return torch.cuda.memory_stats()["allocation.all.allocated"]         # allocations so far, the allocator's cache hits included
+
+
+def _run(variant, watch=None):
     """{name: value} of one variant: "a" unguarded, "b" max_grad_norm=1.0 + skip_nonfinite, "c" = b + a WeightEMA updated after every
-    step and exchanged twice at the end."""
+    step and exchanged twice at the end.  `watch` (a dict): receives "allocated", the allocations made inside each step (the
+    optimiser's and the average's, not the gradients'), and "params"."""
     from mdx.optim import Adam, WeightEMA
     gen = torch.Generator().manual_seed(20240519)
     shapes = GROUP0 + GROUP1
@@ -68,10 +78,14 @@ def _run(variant):
             if step == 2 and variant != "a" and i == 3:
                 g.view(-1)[4100] = float("inf")                   # a gradient VALUE only
             p.grad = None if (step == 4 and i == DROPPED) else _place(g)
+        before = _allocations()
         optimizer.step()
         if ema is not None:
             holder.running.add_(0.5)
             ema.update(optimizer)
+        if watch is not None:
+            watch.setdefault("allocated", []).append(_allocations() - before)
+            watch["params"] = params
     h = hashlib.sha256()
     for p in params:
         st = optimizer.state[p]
@@ -112,3 +126,81 @@ def test_the_bits_are_those_recorded(variant):
     got = _run(variant)
     print(variant, got)
     assert got == RECORDED[variant]
+
+
+# ---- what a capture would see: the entry points called and the allocations made, step by step ------------------------------------
+# (entry point, first, count, nblocks) of every call that takes a plan -- mdx_adam_guard_finish: (0, ntensors, npartials);
+# mdx_ema_tick: zeros -- and the allocations of each step, recorded as RECORDED was: by this file's code on the build of
+# commit 73278bc.  A step that rebuilds no plan allocates nothing; step 1 creates Adam's state and the first plans; steps 4 and 5
+# rebuild (one parameter loses its gradient and has it again).
+_ARGS = {"mdx_adam_step": (1, 2, 5), "mdx_adam_grad_sumsq": (1, 2, 5), "mdx_adam_step_guarded": (1, 2, 5), "mdx_adam_guard_finish": (None, 1, 3),
+         "mdx_ema_update": (1, 2, 4), "mdx_ema_swap": (1, 2, 4), "mdx_ema_tick": (None, None, None), "mdx_digest_words": (1, 2, 4)}
+
+
+class _Recorder(object):
+    """mdx.optim.api with a note of every multi-tensor call; everything is forwarded to the real one."""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    def __getattr__(self, name):
+        fn = getattr(self.real, name)
+        if name not in _ARGS:
+            return fn
+
+        def call(*args):
+            self.calls.append((name[4:],) + tuple(0 if k is None else int(args[k]) for k in _ARGS[name]))
+            return fn(*args)
+        return call
+
+
+def _observe(variant, monkeypatch):
+    import mdx.optim
+    from mdx.optim import WeightDigest
+    rec, watch = _Recorder(mdx.optim.api), {}
+    monkeypatch.setattr(mdx.optim, "api", rec)
+    _run(variant, watch)
+    steps = len(rec.calls)
+    before = _allocations()
+    digest = WeightDigest([p.detach() for p in watch["params"]])
+    built = _allocations() - before
+    digest.compute()
+    return {"calls": rec.calls[:steps], "allocated": watch["allocated"], "digest_calls": rec.calls[steps:],
+            "digest_allocated": [built, _allocations() - before - built]}
+
+
+def _named(name, launches):
+    return [(name,) + launch for launch in launches]
+
+
+# (first, count, nblocks) of the launches of one pass, steps 1-3 and 5 | step 4 (387 tensors in group 0, 391 in all)
+_PLAIN = [(0, 384, 385), (384, 4, 4), (0, 4, 5)], [(0, 384, 385), (384, 3, 3), (0, 4, 5)]            # a table per group: group 1 starts at 0
+_GUARDED = [(0, 384, 385), (384, 4, 4), (388, 4, 5)], [(0, 384, 385), (384, 3, 3), (387, 4, 5)]      # one table: group 1 follows group 0
+_FINISH = ("adam_guard_finish", 0, 392, 394), ("adam_guard_finish", 0, 391, 393)                     # (ntensors, npartials)
+_AVERAGE = [(0, 384, 385), (384, 9, 10)]                                                             # 392 parameters and the buffer
+
+
+def _step_calls(variant, dropped):
+    if variant == "a":
+        return _named("adam_step", _PLAIN[dropped])
+    calls = _named("adam_grad_sumsq", _GUARDED[dropped]) + [_FINISH[dropped]] + _named("adam_step_guarded", _GUARDED[dropped])
+    return calls + (_named("ema_update", _AVERAGE) + [("ema_tick", 0, 0, 0)] if variant == "c" else [])
+
+
+def _seen(variant, allocated):
+    calls = [c for step in range(1, STEPS + 1) for c in _step_calls(variant, step == 4)]
+    return {"calls": calls + (2 * _named("ema_swap", _AVERAGE) if variant == "c" else []), "allocated": allocated,
+            "digest_calls": _named("digest_words", [(0, 384, 385), (384, 8, 9)]), "digest_allocated": [4, 0]}
+
+
+# allocations per step.  Step 1: Adam's state (3 per parameter) and the first plans.  Steps 2 and 3: none.  Steps 4 and 5, plain:
+# group 0's table and two block maps; guarded: the table, three block maps and the partials (the record stays).  The digest:
+# table, two block maps and the output in the constructor, nothing in compute().
+SEEN = {"a": _seen("a", [1181, 0, 0, 3, 3]), "b": _seen("b", [1182, 0, 0, 5, 5]), "c": _seen("c", [1182, 0, 0, 5, 5])}
+
+
+@pytest.mark.parametrize("variant", ["a", "b", "c"])
+def test_the_calls_and_allocations_are_those_recorded(variant, monkeypatch):
+    got = _observe(variant, monkeypatch)
+    print(variant, got)
+    assert got == SEEN[variant]
