@@ -17,9 +17,14 @@ step by csrc/ema.hip -- capturable with the step, its decay warm-up and the guar
 the live weights in place for validation and checkpoints (`swap()`, `applied()`).
 
 `WeightDigest(tensors, names)`: one 64-bit digest per tensor by csrc/digest.hip -- a read-only pass, an integer sum without order or
-tolerance -- for the replica check of a data-parallel run and the checkpoint verification of a resumed one."""
+tolerance -- for the replica check of a data-parallel run and the checkpoint verification of a resumed one.
+
+`GradStats(params, names)`: per-tensor norms, largest magnitudes and counts of non-finite and zero elements of every parameter and
+its gradient by csrc/tensor_stats.hip -- a read-only, capturable, deterministic pass with a per-tensor history kept on the device --
+for finding the layer behind a skipped or clipped step."""
 import contextlib
 import ctypes as C
+import math
 import struct
 
 import torch
@@ -540,3 +545,187 @@ class WeightDigest(object):
         if _capturing():
             raise _lib.MdxError("mdx.optim.WeightDigest.host() synchronises and the current stream is being captured")
         return {n: int(d) & 0xFFFFFFFFFFFFFFFF for n, d in zip(self.names, self.compute().cpu().tolist())}
+
+
+class _StatsTable(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("n", C.c_int64)]
+
+
+class TensorStats(C.Structure):            # include/mdx.h: mdx_tensor_stats
+    _fields_ = [("grad_sumsq", C.c_double), ("weight_sumsq", C.c_double), ("grad_absmax", C.c_float), ("weight_absmax", C.c_float),
+                ("grad_nonfinite", C.c_uint32), ("weight_nonfinite", C.c_uint32), ("grad_zeros", C.c_uint32),
+                ("grad_present", C.c_uint32)]
+
+
+class TensorStatsHistory(C.Structure):     # include/mdx.h: mdx_tensor_stats_history
+    _fields_ = [("passes", C.c_int64), ("bad_passes", C.c_int64), ("first_bad_pass", C.c_int64), ("last_bad_pass", C.c_int64),
+                ("first_bad_weight_pass", C.c_int64), ("max_grad_sumsq", C.c_double), ("max_grad_pass", C.c_int64)]
+
+
+class GradStats(object):
+    """Per-tensor statistics of every parameter of `params` and its gradient, for finding the layer: where the step guard reports one
+    global norm, `compute()` gives each tensor a record (include/mdx.h: mdx_tensor_stats) -- the sums of squares of the FINITE
+    elements of gradient and weight, their largest finite magnitudes, the counts of non-finite elements and of gradient elements
+    equal to zero -- and advances a per-tensor history (mdx_tensor_stats_history: passes, passes with a non-finite gradient and
+    the first and last of them, the first pass with a non-finite weight, the largest gradient norm and its pass).  The pass only
+    reads: `.grad` is taken where the step left it and never written.  A guarded optimiser consumes g * coef without storing it,
+    so these are the statistics of the UNCLIPPED gradients.
+
+    Dense float32 GPU parameters on one device, contiguous or channels-last, with gradients that are float32 and have their
+    parameter's strides (or are None: no gradient this pass) go through csrc/tensor_stats.hip: the table, block maps, slot
+    offsets, partials, records, history and the gradient-pointer arrays are built HERE, nothing is allocated later, `compute()`
+    launches without synchronising and is capturable, the history stays on the device, and the same inputs give the same bits.
+    Anything else -- CPU parameters, `native = False`, a gradient of another dtype or layout -- takes torch's own functions in
+    float64, which read on the host and cannot be captured; the records and the history are the same.  `host()`, `total_norm()`
+    and `history()` are the only calls that synchronise.  The parameters must keep their storage.  The history belongs to this
+    object: it is no part of any state_dict and does not survive a resumed run.  `names` default to "0", "1", ..."""
+
+    native = True          # False: torch's own functions for every pass
+
+    def __init__(self, params, names=None):
+        if _capturing():
+            raise _lib.MdxError("mdx.optim.GradStats: built while the current stream is being captured")
+        self.params = list(params)
+        self.tensors = [p.detach() for p in self.params]
+        self.names = [str(i) for i in range(len(self.params))] if names is None else [str(n) for n in names]
+        if not self.params:
+            raise ValueError("GradStats: no parameters")
+        if len(self.names) != len(self.params) or len(set(self.names)) != len(self.names):
+            raise ValueError("GradStats: %d parameters need %d distinct names" % (len(self.params), len(self.params)))
+        n = len(self.params)
+        assert C.sizeof(TensorStats) == 40 and C.sizeof(TensorStatsHistory) == 56
+        self._native = self._last_native = self._native_ok()          # _last_native: did the last pass take the kernels?
+        self._table = self._launches = self._offsets = self._partials = None
+        dev = self.tensors[0].device if self._native else torch.device("cpu")
+        # 40 bytes = 5 words and 56 bytes = 7 words of 8: int64 storage is 8-byte aligned and all-zero is the history's initial state
+        self._records = torch.zeros(n, 5, dtype=torch.int64, device=dev)
+        self._history = torch.zeros(n, 7, dtype=torch.int64, device=dev)
+        if self._native:
+            assert (api.mdx_tensor_stats_table_entry_bytes(), api.mdx_tensor_stats_partial_bytes(), api.mdx_tensor_stats_record_bytes(),
+                    api.mdx_tensor_stats_history_bytes()) == (C.sizeof(_StatsTable), 40, 40, 56)
+            host = (_StatsTable * n)()
+            for i, t in enumerate(self.tensors):
+                host[i] = _StatsTable(t.data_ptr(), t.numel())
+            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
+            chunk = api.mdx_adam_chunk()
+            offsets = [0]
+            for t in self.tensors:
+                offsets.append(offsets[-1] + (t.numel() + chunk - 1) // chunk)
+            if offsets[-1] >= 1 << 31:
+                raise ValueError("GradStats: %d chunks of %d elements do not fit the int32 slot offsets" % (offsets[-1], chunk))
+            self._offsets = torch.tensor(offsets, dtype=torch.int32).to(dev)
+            # each launch with the slot its slice of the partials starts at and its own host array of gradient pointers
+            self._launches = [(first, count, blockmap, nblocks, offsets[first], (C.c_void_p * count)())
+                              for first, count, blockmap, nblocks in Adam._launches(self.tensors, 0)]
+            self._partials = torch.empty(offsets[-1], 5, dtype=torch.int64, device=dev)
+            self._key = tuple(t.data_ptr() for t in self.tensors)
+
+    def _native_ok(self):
+        if not self.native:
+            return False
+        dev = self.tensors[0].device
+        return all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.numel() > 0 and not t.is_sparse
+                   and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) for t in self.tensors)
+
+    def _grads_native(self, grads):
+        dev = self.tensors[0].device
+        return all(g is None or (g.is_cuda and g.device == dev and g.dtype == torch.float32 and not g.is_sparse and Adam._dense(g, t))
+                   for g, t in zip(grads, self.tensors))
+
+    def _check_native(self):
+        dev = self.tensors[0].device
+        if dev.index != torch.cuda.current_device():
+            raise _lib.MdxError("mdx.optim.GradStats: parameters live on %s but the current device is cuda:%d"
+                                % (dev, torch.cuda.current_device()))
+        if tuple(t.data_ptr() for t in self.tensors) != self._key:
+            raise _lib.MdxError("mdx.optim.GradStats: a parameter has changed its storage since construction")
+
+    @staticmethod
+    def _torch_record(w, g):
+        """One tensor's record by torch's own functions, sums in float64."""
+        def half(t):
+            t = t.detach()
+            finite = torch.isfinite(t)
+            kept = t[finite].double()
+            return (float((kept * kept).sum()), float(kept.abs().max()) if kept.numel() else 0.0, int((~finite).sum()),
+                    int((t == 0).sum()))
+        wsum, wmax, wnf, _ = half(w)
+        gsum, gmax, gnf, gz = half(g) if g is not None else (0.0, 0.0, 0, 0)
+        return TensorStats(gsum, wsum, gmax, wmax, gnf & 0xFFFFFFFF, wnf & 0xFFFFFFFF, gz & 0xFFFFFFFF, int(g is not None))
+
+    def _torch_compute(self, grads):
+        if _capturing() and (self._records.is_cuda or any(t.is_cuda for t in self.tensors)):
+            raise _lib.MdxError("mdx.optim.GradStats: the torch path reads the tensors on the host and cannot be captured")
+        n = len(self.tensors)
+        recs = (TensorStats * n)(*[self._torch_record(t, g) for t, g in zip(self.tensors, grads)])
+        hist = (TensorStatsHistory * n).from_buffer_copy(self._history.cpu().numpy().tobytes())
+        for r, h in zip(recs, hist):                       # include/mdx.h: mdx_tensor_stats_finish
+            h.passes += 1
+            if r.grad_nonfinite > 0:
+                h.bad_passes += 1
+                h.first_bad_pass = h.first_bad_pass or h.passes
+                h.last_bad_pass = h.passes
+            if r.weight_nonfinite > 0:
+                h.first_bad_weight_pass = h.first_bad_weight_pass or h.passes
+            if r.grad_present and r.grad_sumsq > h.max_grad_sumsq:
+                h.max_grad_sumsq, h.max_grad_pass = r.grad_sumsq, h.passes
+        self._records.copy_(torch.frombuffer(bytearray(bytes(recs)), dtype=torch.int64).view(n, 5))
+        self._history.copy_(torch.frombuffer(bytearray(bytes(hist)), dtype=torch.int64).view(n, 7))
+
+    @torch.no_grad()
+    def compute(self, grads=None):
+        """One pass over `grads` (default: every parameter's .grad as it is now; None entries are parameters without a gradient)
+        -> the record buffer (int64 [tensors, 5]: the 40 bytes of each mdx_tensor_stats; the same tensor at every call), on the
+        parameters' device without a synchronisation on the native path, on the host otherwise."""
+        grads = [p.grad for p in self.params] if grads is None else list(grads)
+        if len(grads) != len(self.params):
+            raise ValueError("GradStats: %d gradients for %d parameters" % (len(grads), len(self.params)))
+        self._last_native = self._native and self._grads_native(grads)
+        if not self._last_native:
+            self._torch_compute(grads)
+            return self._records
+        self._check_native()
+        table, partials, s = self._table.data_ptr(), self._partials.data_ptr(), stream()
+        for first, count, blockmap, nblocks, slot, garr in self._launches:
+            for i in range(count):
+                g = grads[first + i]
+                garr[i] = None if g is None else g.data_ptr()
+            api.mdx_tensor_stats_partials(table, first, count, garr, blockmap.data_ptr(), nblocks, partials + 40 * slot, s)
+        for first, count, _, _, _, _ in self._launches:
+            api.mdx_tensor_stats_finish(first, count, self._offsets.data_ptr(), partials, self._records.data_ptr(),
+                                        self._history.data_ptr(), s)
+        return self._records
+
+    def _read(self, what, buf, struct_type):
+        if _capturing():
+            raise _lib.MdxError("mdx.optim.GradStats.%s() synchronises and the current stream is being captured" % what)
+        return (struct_type * len(self.tensors)).from_buffer_copy(buf.cpu().numpy().tobytes())
+
+    def host(self):
+        """{name: {grad_norm, weight_norm, grad_absmax, weight_absmax, grad_nonfinite, weight_nonfinite, grad_zeros, grad_present,
+        numel}} of the last pass; the square roots are taken here, in double.  Reads the records: synchronises, computes nothing."""
+        out = {}
+        for n, t, r in zip(self.names, self.tensors, self._read("host", self._records, TensorStats)):
+            out[n] = dict(grad_norm=math.sqrt(r.grad_sumsq), weight_norm=math.sqrt(r.weight_sumsq), grad_absmax=r.grad_absmax,
+                          weight_absmax=r.weight_absmax, grad_nonfinite=r.grad_nonfinite, weight_nonfinite=r.weight_nonfinite,
+                          grad_zeros=r.grad_zeros, grad_present=r.grad_present, numel=t.numel())
+        return out
+
+    def total_norm(self):
+        """The L2 norm of every finite gradient element of the last pass, in double.  Synchronises."""
+        return math.sqrt(math.fsum(r.grad_sumsq for r in self._read("total_norm", self._records, TensorStats)))
+
+    def history(self):
+        """{name: {passes, bad_passes, first_bad_pass, last_bad_pass, first_bad_weight_pass, max_grad_norm, max_grad_pass}} since
+        construction or the last reset_history(); pass numbers are 1-based, 0 is "never".  Synchronises."""
+        out = {}
+        for n, h in zip(self.names, self._read("history", self._history, TensorStatsHistory)):
+            out[n] = dict(passes=h.passes, bad_passes=h.bad_passes, first_bad_pass=h.first_bad_pass, last_bad_pass=h.last_bad_pass,
+                          first_bad_weight_pass=h.first_bad_weight_pass, max_grad_norm=math.sqrt(h.max_grad_sumsq),
+                          max_grad_pass=h.max_grad_pass)
+        return out
+
+    def reset_history(self):
+        if _capturing():
+            raise _lib.MdxError("mdx.optim.GradStats.reset_history() is not part of a pass and the current stream is being captured")
+        self._history.zero_()

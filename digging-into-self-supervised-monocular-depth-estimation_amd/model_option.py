@@ -78,6 +78,13 @@ def options(argv=None):
                         "weights on the device (mdx/optim.py: WeightDigest, csrc/digest.hip) and, in a data-parallel run, compare the "
                         "digests across the ranks (one int64 all-reduce; a difference raises on every rank); state<N>.pt records the "
                         "digests and --resume verifies the weight files against them; 0: off")
+    p.add_argument("--grad_stats", type=int, default=0,
+                   help="N > 0: after every N-th step, one read-only pass on the device over every trained parameter and its gradient "
+                        "(mdx/optim.py: GradStats, csrc/tensor_stats.hip): per-tensor norms, largest magnitudes, counts of non-finite "
+                        "and zero elements, and a per-tensor history kept on the device and read once per epoch -- rank 0 prints the "
+                        "tensors with the largest and smallest gradient norm, names the tensors whose gradients or weights went "
+                        "non-finite with the step it first happened, and appends a line to ./model_save/<save>/grad_stats.jsonl.  "
+                        "The gradients are the unclipped ones; the history is not saved and does not survive --resume; 0: off")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

@@ -172,12 +172,21 @@ class setting(object):
         if decay > 0:
             from mdx.optim import WeightEMA
             self.optim["ema"] = WeightEMA(self.raw_model.values(), decay, warmup=bool(_opt(self.opt, "ema_warmup", 1)))
-        # --check_weights (off by default): digests of the trained float32 master parameters, for the replica check and the
-        # checkpoint verification.  Batch-norm statistics are per rank by design (set_model) and are left out.
-        if int(_opt(self.opt, "check_weights", 0) or 0) > 0:
-            from mdx.optim import WeightDigest
+        # --check_weights and --grad_stats (both off by default) go over the trained float32 master parameters, named
+        # "<network>.<parameter>"; with both off nothing is built here
+        check, stats = int(_opt(self.opt, "check_weights", 0) or 0) > 0, int(_opt(self.opt, "grad_stats", 0) or 0) > 0
+        if check or stats:
             name = {id(p): "%s.%s" % (key, n) for key, m in self.raw_model.items() for n, p in m.named_parameters()}
-            self.optim["digest"] = WeightDigest(self.parameters, [name[id(p)] for p in self.parameters])
+            names = [name[id(p)] for p in self.parameters]
+        # --check_weights: digests of the parameters, for the replica check and the checkpoint verification.  Batch-norm statistics
+        # are per rank by design (set_model) and are left out.
+        if check:
+            from mdx.optim import WeightDigest
+            self.optim["digest"] = WeightDigest(self.parameters, names)
+        # --grad_stats: per-tensor statistics of the parameters and their gradients; nothing is launched, printed or written without it
+        if stats:
+            from mdx.optim import GradStats
+            self.optim["grad_stats"] = GradStats(self.parameters, names)
 
     def set_train(self):
         for value in self.model.values():

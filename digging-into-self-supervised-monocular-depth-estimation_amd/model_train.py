@@ -4,6 +4,7 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 model_train.py ...
 """
 import contextlib
+import json
 import os
 import sys
 
@@ -267,6 +268,9 @@ class trainer(object):
         self.opt = opt
         self._graphed = None
         self._graphed_valid = None
+        # --grad_stats: the passes issued so far, how many of them did not take the kernels, and {pass: training step} for the
+        # passes a report may have to name (grad_stats_report drops the others)
+        self._grad_stat_passes, self._grad_stat_torch, self._grad_stat_steps = 0, 0, {}
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if torch.cuda.is_available():
@@ -381,6 +385,66 @@ class trainer(object):
             check_replicas(digest)
             self._weight_checks += 1
 
+    def grad_stats(self, step=None):
+        """--grad_stats: one pass of per-tensor statistics (mdx/optim.py: GradStats) over the float32 master parameters and the
+        gradients the step just consumed, read from `.grad` where the step left them -- the eager step's own tensors, a captured
+        step's graph tensors after the last replay, the views into the flat buffer after the exchange of a data-parallel step.
+        Eager launches on the current stream, behind the step or its replay, never inside a graph; nothing synchronises.  `.grad`
+        is only read, and the guard consumes g * coef without storing it: these are the statistics of the UNCLIPPED gradients.
+        `step`: the number of the training step behind which the pass runs, kept so that the report can name the step of a pass.
+        The history lives on the device in this trainer's GradStats object alone: it is not part of state_dict(), not written
+        to state<N>.pt, and a resumed run starts a new one."""
+        stats = self.setting.optim.get("grad_stats")
+        if stats is not None:
+            stats.compute()
+            self._grad_stat_passes += 1
+            self._grad_stat_torch += int(stats._native and not stats._last_native)
+            self._grad_stat_steps[self._grad_stat_passes] = step
+
+    def grad_stats_report(self):
+        """-> (the lines rank 0 prints after an epoch, the record it appends to grad_stats.jsonl).  Reads the device records and
+        history: the one place of --grad_stats that synchronises."""
+        stats = self.setting.optim["grad_stats"]
+        passes, steps = self._grad_stat_passes, self._grad_stat_steps
+        if not passes:
+            return ["grad stats: 0 passes"], dict(passes=0, records={}, history={})
+        host, hist, total = stats.host(), stats.history(), stats.total_norm()
+        # the device counts the passes of each tensor, the trainer the passes it issued: the step of a pass is known only while the
+        # two agree (they part when somebody else calls compute() or reset_history() on the trainer's object)
+        in_step = all(h["passes"] == passes for h in hist.values())
+
+        def step_of(p):                                   # the training step of pass p (1-based; 0: never)
+            return steps.get(p) if in_step and p > 0 else None
+        seen = [(r["grad_norm"], n) for n, r in host.items() if r["grad_present"]]
+        line = "grad stats: %d passes, last gradient norm %g" % (passes, total)
+        if seen:
+            line += ", largest %s %g, smallest %s %g" % (max(seen)[1], max(seen)[0], min(seen)[1], min(seen)[0])
+        if self._grad_stat_torch:                         # a gradient without its parameter's dtype or strides: read on the host
+            line += "; %d passes took torch's functions, not the kernels" % self._grad_stat_torch
+        if not in_step:
+            line += "; the history was advanced or reset outside the trainer: steps unknown"
+        lines = [line]
+        bad = [n for n in stats.names if hist[n]["bad_passes"] > 0]
+        if bad:
+            lines.append("grad stats: non-finite gradients in %d tensors: %s%s" % (len(bad), ", ".join(
+                "%s (first at step %s, %d of %d passes)" % (n, step_of(hist[n]["first_bad_pass"]), hist[n]["bad_passes"], hist[n]["passes"])
+                for n in bad[:5]), ", ..." if len(bad) > 5 else ""))
+        badw = [n for n in stats.names if hist[n]["first_bad_weight_pass"] > 0]
+        if badw:
+            lines.append("grad stats: non-finite weights in %d tensors: %s%s" % (len(badw), ", ".join(
+                "%s (first at step %s)" % (n, step_of(hist[n]["first_bad_weight_pass"])) for n in badw[:5]),
+                ", ..." if len(badw) > 5 else ""))
+        keys = (("first_bad_pass", "first_bad_step"), ("last_bad_pass", "last_bad_step"), ("first_bad_weight_pass", "first_bad_weight_step"),
+                ("max_grad_pass", "max_grad_step"))
+        for h in hist.values():
+            h.update({name: step_of(h[key]) for key, name in keys})
+        record = dict(passes=passes, torch_passes=self._grad_stat_torch, last_step=steps.get(passes), total_norm=total, records=host,
+                      history=hist)
+        # only the passes the history points at (and the last one) can be asked for again: the table does not grow with the run
+        keep = {h[key] for h in hist.values() for key, _ in keys} | {passes}
+        self._grad_stat_steps = {p: st for p, st in steps.items() if p in keep} if in_step else {}
+        return lines, record
+
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
         (--noise cpu: torch.randn on the CPU + a copy from pageable memory), not with a non-RCCL process group.  With more than
@@ -436,6 +500,9 @@ class trainer(object):
         # N-th step of the run and before each checkpoint
         every, done = int(getattr(self.opt, "check_weights", 0) or 0), 0
         self.check_weights()
+        # --grad_stats N: per-tensor gradient and weight statistics behind every N-th step of the run; every rank computes (the
+        # ranks stay in step), rank 0 alone reads and reports, once per epoch
+        stats_every = int(getattr(self.opt, "grad_stats", 0) or 0) if "grad_stats" in self.setting.optim else 0
         for epoch in range(start, self.opt.epoch):
             batch_train = {k: [] for k in names}
             batch_valid = {k: [] for k in names}
@@ -449,6 +516,8 @@ class trainer(object):
                 done += 1
                 if every > 0 and done % every == 0:
                     self.check_weights()
+                if stats_every > 0 and done % stats_every == 0:
+                    self.grad_stats(done)
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
@@ -480,6 +549,13 @@ class trainer(object):
                     g = optimizer.guard_stats()
                     print("step guard: %d steps, %d skipped, last gradient norm %g" % (g["steps"], g["skipped_steps"], g["total_norm"]),
                           flush=True)
+                if stats_every > 0:
+                    lines, record = self.grad_stats_report()
+                    print("\n".join(lines), flush=True)
+                    directory = os.path.join("./model_save", self.opt.save)
+                    os.makedirs(directory, exist_ok=True)
+                    with open(os.path.join(directory, "grad_stats.jsonl"), "a") as f:
+                        f.write(json.dumps(dict(epoch=epoch + 1, **record)) + "\n")
                 if ema is not None:
                     e = ema.stats()
                     print("weight EMA: %d updates, %d held" % (e["updates"], e["held"]), flush=True)

@@ -308,6 +308,51 @@ int mdx_ema_swap(const void *table, int first, int count, const void *blockmap, 
 size_t mdx_digest_table_entry_bytes(void);
 int mdx_digest_words(const void *table, int first, int count, const void *blockmap, int nblocks, uint64_t *out, void *stream);
 
+/* Per-tensor gradient and weight statistics, computed on the device (csrc/tensor_stats.hip; mdx.optim.GradStats): where the step
+ * guard knows one global norm, this read-only pass says which tensor.  table: DEVICE array of { const float *weight; int64_t numel }
+ * (mdx_tensor_stats_table_entry_bytes() = 16 each; the parameter's dense storage); first / count / blockmap / nblocks as for
+ * mdx_adam_step (count <= mdx_adam_max_tensors(), chunks of mdx_adam_chunk() elements); grads: HOST array of count device pointers
+ * as for mdx_adam_grad_sumsq, except that an entry may be NULL: that parameter received no gradient in this pass.
+ *   mdx_tensor_stats_partials  block b writes the record of its chunk -- an mdx_tensor_stats over the chunk's elements alone -- to
+ *                              slot b of partials (DEVICE, nblocks slots of mdx_tensor_stats_partial_bytes() = 40, 8-byte aligned).
+ *                              Several calls (more than mdx_adam_max_tensors() tensors) take disjoint slices of one partials buffer,
+ *                              in table order, so that tensor t's slots are offsets[t] .. offsets[t + 1] - 1 of the whole buffer.
+ *                              An element is finite when its exponent bits are not all ones; a square is formed and added in
+ *                              double (exact, and 1e30 squared stays finite); a zero is +0 or -0; a magnitude is compared by its
+ *                              bits, so denormals count whatever the denormal mode.  A NULL gradient: the weight half alone.
+ *   mdx_tensor_stats_finish    one block per tensor first .. first + count - 1: adds the tensor's slots of partials (the WHOLE
+ *                              buffer's base) in a fixed order -- offsets: DEVICE array of int32, one more than there are tensors --
+ *                              and writes records[t] (DEVICE, mdx_tensor_stats_record_bytes() = 40 each, 8-byte aligned).  With
+ *                              history (DEVICE, mdx_tensor_stats_history_bytes() = 56 each, 8-byte aligned, zeroed once by the
+ *                              caller; or NULL) it advances history[t]: passes += 1; grad_nonfinite > 0 counts a bad pass and
+ *                              sets first / last; weight_nonfinite > 0 sets first_bad_weight_pass once; a gradient that is present
+ *                              and whose grad_sumsq exceeds max_grad_sumsq sets it and max_grad_pass (the first pass of a tie).
+ * Every slot, record and history entry is written by exactly one thread with plain stores: no atomics, nothing to clear, the same
+ * inputs give the same bits at every launch, and the pair is capturable and replayable.  Nothing but the three outputs is written. */
+typedef struct mdx_tensor_stats {          /* 40 bytes */
+    double grad_sumsq, weight_sumsq;       /* over FINITE elements only */
+    float grad_absmax, weight_absmax;      /* over finite elements; 0 when there is none */
+    uint32_t grad_nonfinite, weight_nonfinite, grad_zeros;   /* counts modulo 2^32 */
+    uint32_t grad_present;                 /* 0: no gradient pointer was given; the grad_* fields are 0 */
+} mdx_tensor_stats;
+
+typedef struct mdx_tensor_stats_history {  /* 56 bytes; all-zero is the valid initial state */
+    int64_t passes, bad_passes;            /* bad: grad_nonfinite > 0 */
+    int64_t first_bad_pass, last_bad_pass; /* 1-based pass numbers of this tensor; 0 = never */
+    int64_t first_bad_weight_pass;         /* first pass with weight_nonfinite > 0; 0 = never */
+    double max_grad_sumsq;                 /* the largest grad_sumsq of a pass with a gradient; over finite elements, so finite */
+    int64_t max_grad_pass;                 /* that pass; 0 = none yet (no gradient, or only zero ones) */
+} mdx_tensor_stats_history;
+
+size_t mdx_tensor_stats_table_entry_bytes(void);
+size_t mdx_tensor_stats_partial_bytes(void);
+size_t mdx_tensor_stats_record_bytes(void);
+size_t mdx_tensor_stats_history_bytes(void);
+int mdx_tensor_stats_partials(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
+                              void *partials, void *stream);
+int mdx_tensor_stats_finish(int first, int count, const int *offsets, const void *partials, void *records, void *history,
+                            void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fine-grained ops behind the reference's model_layer / model_loss API (each differentiable)
  * ---------------------------------------------------------------------------------------- */
