@@ -195,7 +195,8 @@ class noise_state(object):
     """Device-resident {seed, offset} of the kernel-side N(0,1) generator (csrc/photo_prologue.hip: Philox4x32-10 keyed by
     the seed, counter = (pixel, draw, offset)).  The offset is advanced ON THE DEVICE by the step's finishing kernel, so
     a captured step draws new numbers at every replay and nothing on the host takes part.  seed: torch.initial_seed()
-    (what torch.manual_seed set) + `stream` (the data-parallel rank: ranks draw different noise)."""
+    (what torch.manual_seed set) + 0x9E3779B97F4A7C15 * `stream` (the data-parallel rank: ranks draw different noise),
+    mod 2^63.  The stream a {seed, offset} gives is pinned value by value (tests/philox_ref.py, tests/test_gpu_noise_pin.py)."""
 
     def __init__(self, device, seed=None, stream=0):
         seed = (torch.initial_seed() if seed is None else int(seed)) + 0x9E3779B97F4A7C15 * int(stream)

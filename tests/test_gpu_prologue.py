@@ -7,7 +7,9 @@
   * drawn noise (what a training step uses): N(0,1) -- moments, independence over pixels / frames / scales / steps --
     reproducible for a given {seed, offset}, advanced on the device by the step itself.
 The reference draws torch.randn on the HOST (processor.py:195); no device generator can reproduce that stream, the
-distribution is what the auto-mask depends on.
+distribution is what the auto-mask depends on: this file holds the distribution.  The kernel's OWN stream -- which
+numbers a {seed, offset} gives -- is pinned too, value by value against a numpy Philox4x32-10 + float64 Box-Muller, in
+tests/test_gpu_noise_pin.py (the reference generator: tests/philox_ref.py, itself held to the Random123 vectors).
 """
 import numpy as np
 import pytest
@@ -35,7 +37,13 @@ def _case(G, B, H, W, S, nscales, seed=3):
 
 
 @pytest.mark.parametrize("B,H,W,S,nscales", [(2, 192, 640, 2, 4), (1, 192, 640, 3, 4), (1, 100, 150, 2, 1),
-                                             (3, 64, 68, 1, 4), (1, 192, 640, 4, 2)])
+                                             (3, 64, 68, 1, 4), (1, 192, 640, 4, 2),
+                                             # the smallest sizes; every one of them runs the training-kernel half too
+                                             # (_case: disparity maps at H >> s x W >> s where 8 divides both, else at H x W)
+                                             (1, 4, 4, 1, 1),        # the smallest image the descriptor admits
+                                             (2, 5, 7, 2, 2),        # odd, smaller than a tile, two images
+                                             (1, 8, 64, 3, 4),       # exactly one 64x8 tile, 16-byte loads; disparities down to 1x8
+                                             (1, 9, 65, 4, 4)])      # one pixel into the next tile in both directions
 def test_prologue_injected_noise_matches_per_op_results(G, B, H, W, S, nscales):
     tgt, srcs, disps, noises, P, invK = _case(G, B, H, W, S, nscales)
     pre = G.F.photometric_prologue(tgt, srcs, nscales, noises=noises, need_ident=True)
