@@ -85,6 +85,16 @@ def options(argv=None):
                         "tensors with the largest and smallest gradient norm, names the tensors whose gradients or weights went "
                         "non-finite with the step it first happened, and appends a line to ./model_save/<save>/grad_stats.jsonl.  "
                         "The gradients are the unclipped ones; the history is not saved and does not survive --resume; 0: off")
+    p.add_argument("--loss_stats", type=int, default=0,
+                   help="N > 0: after every N-th step, one read-only pass on the device over the maps the loss path leaves behind "
+                        "(mdx/loss_stats.py: LossStats, csrc/loss_stats.hip): per scale and image the share of the pixels the auto-mask "
+                        "removed, the share each source frame won, the range of the disparity, counts of corrupt indices and non-finite "
+                        "disparities, and a per-scale history kept on the device and read once per epoch -- rank 0 prints one line per "
+                        "scale and appends a line to ./model_save/<save>/loss_stats.jsonl.  The history is not saved and does not "
+                        "survive --resume; 0: off")
+    p.add_argument("--loss_stats_static", type=float, default=0.9,
+                   help="--loss_stats: an image counts as static when at least this share of its pixels is auto-masked (a reporting "
+                        "threshold, in (0, 1])")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

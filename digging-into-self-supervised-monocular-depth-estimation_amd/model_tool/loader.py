@@ -188,6 +188,14 @@ class setting(object):
             from mdx.optim import GradStats
             self.optim["grad_stats"] = GradStats(self.parameters, names)
 
+        # --loss_stats: statistics of the maps the loss path leaves behind, for the training shapes; nothing is built without it
+        if int(_opt(self.opt, "loss_stats", 0) or 0) > 0:
+            from mdx.loss_stats import LossStats
+            o = self.opt
+            self.optim["loss_stats"] = LossStats(o.batch, o.height, o.width, len(o.frame_ids) - 1,
+                                                 [(o.height >> k, o.width >> k) for k in o.scales], bool(o.use_automasking),
+                                                 float(_opt(o, "loss_stats_static", 0.9)), device=self.device)
+
     def set_train(self):
         for value in self.model.values():
             value.train()

@@ -271,6 +271,9 @@ class trainer(object):
         # --grad_stats: the passes issued so far, how many of them did not take the kernels, and {pass: training step} for the
         # passes a report may have to name (grad_stats_report drops the others)
         self._grad_stat_passes, self._grad_stat_torch, self._grad_stat_steps = 0, 0, {}
+        # --loss_stats: the passes issued since the last report (the history is reset with every report), how many of them did not
+        # take the kernels, {pass: training step} for them, and the passes of the whole run
+        self._loss_stat_passes, self._loss_stat_torch, self._loss_stat_steps, self._loss_stat_total = 0, 0, {}, 0
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if torch.cuda.is_available():
@@ -445,6 +448,75 @@ class trainer(object):
         self._grad_stat_steps = {p: st for p, st in steps.items() if p in keep} if in_step else {}
         return lines, record
 
+    def loss_stats(self, outputs, step=None):
+        """--loss_stats: one pass of statistics (mdx/loss_stats.py: LossStats) over the maps the step just left in `outputs`:
+        `("automask", s)`, the arg-min channel of every pixel, and `("disp", s)` -- the eager step's own tensors, a captured step's
+        graph tensors after the last replay.  A scale without an automask entry (one source frame without the auto-mask on the
+        op-by-op path) passes None.  Eager launches on the current stream, behind the step or its replay, never inside a graph;
+        nothing synchronises and the maps are only read.  `step`: the number of the training step behind which the pass runs.  The
+        history lives in this trainer's LossStats object alone: it is not part of any state file and a resumed run starts a new one."""
+        stats = self.setting.optim.get("loss_stats")
+        if stats is not None:
+            stats.compute([outputs.get(("automask", k)) for k in self.opt.scales], [outputs.get(("disp", k)) for k in self.opt.scales])
+            self._loss_stat_passes += 1
+            self._loss_stat_total += 1
+            self._loss_stat_torch += int(stats._native and not stats._last_native)
+            self._loss_stat_steps[self._loss_stat_passes] = step
+
+    def loss_stats_report(self):
+        """-> (the lines rank 0 prints after an epoch, one per scale, and the record it appends to loss_stats.jsonl): the shares are
+        those of the epoch (train() starts the history again after the report), the step numbers those of the run.  Reads the
+        device records and history: the one place of --loss_stats that synchronises."""
+        stats = self.setting.optim["loss_stats"]
+        passes, steps = self._loss_stat_passes, self._loss_stat_steps
+        if not passes:
+            return ["loss stats: 0 passes"], dict(passes=0, scales={})
+        host, hist = stats.host(), stats.history()
+        # the device counts the passes of each scale, the trainer the passes it issued: the step of a pass is known only while the
+        # two agree (they part when somebody else calls compute() or reset_history() on the trainer's object)
+        in_step = all(h["passes"] == passes for h in hist)
+
+        def step_of(p):                                   # the training step of pass p of this epoch (1-based; 0: never)
+            return steps.get(p) if in_step and p > 0 else None
+        ids = [str(f) for f in self.opt.frame_ids[1:]]
+        names = (["identity %s" % f for f in ids] if stats.automask else []) + ["frame %s" % f for f in ids]
+        keys = (("first_bad_pass", "first_bad_step"), ("first_static_pass", "first_static_step"), ("last_static_pass", "last_static_step"),
+                ("max_masked_pass", "max_masked_step"), ("min_disp_range_pass", "min_disp_range_step"))
+        lines, scales = [], {}
+        for scale, rows, h in zip(self.opt.scales, host, hist):
+            h.update({name: step_of(h[key]) for key, name in keys})
+            h["shares"] = dict(zip(names, h["shares"].values()))
+            for r in rows:
+                r["shares"] = dict(zip(names, r["shares"].values()))
+            seen = [r for r in rows if r["disp_present"]]
+            line = "loss stats scale %s: %d passes, masked %.4f, %s" % (
+                scale, h["passes"], h["masked_share"], ", ".join("%s %.4f" % kv for kv in h["shares"].items()))
+            line += "; static images %d of %d" % (h["static_images"], h["images"])
+            if h["static_images"]:
+                line += " (first at step %s)" % h["first_static_step"]
+            if seen:
+                line += "; disparity %g .. %g in the last pass" % (min(r["disp_min"] for r in seen), max(r["disp_max"] for r in seen))
+            if h["min_disp_range_pass"]:
+                line += ", smallest range of an image %g (step %s)" % (h["min_disp_range"], h["min_disp_range_step"])
+            line += "; bad passes %d" % h["bad_passes"]
+            if h["bad_passes"]:
+                line += " (first at step %s)" % h["first_bad_step"]
+            lines.append(line)
+            scales[str(scale)] = dict(history=h, records=rows)
+        if self._loss_stat_torch:                         # int64 indices of the op-by-op path, CPU tensors: read on the host
+            lines.append("loss stats: %d passes took torch's functions, not the kernels" % self._loss_stat_torch)
+        if not in_step:
+            lines.append("loss stats: the history was advanced or reset outside the trainer: steps unknown")
+        record = dict(passes=passes, run_passes=self._loss_stat_total, torch_passes=self._loss_stat_torch, last_step=steps.get(passes),
+                      scales=scales)
+        return lines, record
+
+    def loss_stats_new_epoch(self):
+        """The history starts again, and with it the pass numbers: the shares of the next report are those of its own epoch.  No
+        pass of the last one can be asked for again, so the {pass: step} table is emptied: it does not grow with the run."""
+        self.setting.optim["loss_stats"].reset_history()
+        self._loss_stat_passes, self._loss_stat_torch, self._loss_stat_steps = 0, 0, {}
+
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
         (--noise cpu: torch.randn on the CPU + a copy from pageable memory), not with a non-RCCL process group.  With more than
@@ -503,6 +575,9 @@ class trainer(object):
         # --grad_stats N: per-tensor gradient and weight statistics behind every N-th step of the run; every rank computes (the
         # ranks stay in step), rank 0 alone reads and reports, once per epoch
         stats_every = int(getattr(self.opt, "grad_stats", 0) or 0) if "grad_stats" in self.setting.optim else 0
+        # --loss_stats N: statistics of the loss path's maps behind every N-th step of the run, reported like --grad_stats; the
+        # report covers rank 0's own batches
+        loss_every = int(getattr(self.opt, "loss_stats", 0) or 0) if "loss_stats" in self.setting.optim else 0
         for epoch in range(start, self.opt.epoch):
             batch_train = {k: [] for k in names}
             batch_valid = {k: [] for k in names}
@@ -518,6 +593,8 @@ class trainer(object):
                     self.check_weights()
                 if stats_every > 0 and done % stats_every == 0:
                     self.grad_stats(done)
+                if loss_every > 0 and done % loss_every == 0:
+                    self.loss_stats(train_outputs, done)
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
@@ -556,11 +633,20 @@ class trainer(object):
                     os.makedirs(directory, exist_ok=True)
                     with open(os.path.join(directory, "grad_stats.jsonl"), "a") as f:
                         f.write(json.dumps(dict(epoch=epoch + 1, **record)) + "\n")
+                if loss_every > 0:
+                    lines, record = self.loss_stats_report()
+                    print("\n".join(lines), flush=True)
+                    directory = os.path.join("./model_save", self.opt.save)
+                    os.makedirs(directory, exist_ok=True)
+                    with open(os.path.join(directory, "loss_stats.jsonl"), "a") as f:
+                        f.write(json.dumps(dict(epoch=epoch + 1, **record)) + "\n")
                 if ema is not None:
                     e = ema.stats()
                     print("weight EMA: %d updates, %d held" % (e["updates"], e["held"]), flush=True)
                 if every > 0:
                     print("weight check: %d checks, ranks agree" % self._weight_checks, flush=True)
+            if loss_every > 0:                    # every rank: the shares of the next report are those of its own epoch
+                self.loss_stats_new_epoch()
             self.check_weights()
             self.control.save(epoch, epoch_train, epoch_valid, self.setting, compute=self.compute)
 

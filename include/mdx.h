@@ -353,6 +353,72 @@ int mdx_tensor_stats_partials(const void *table, int first, int count, const flo
 int mdx_tensor_stats_finish(int first, int count, const int *offsets, const void *partials, void *records, void *history,
                             void *stream);
 
+/* Statistics of the maps the fused loss path leaves behind, computed on the device (csrc/loss_stats.hip; mdx.loss_stats.LossStats):
+ * which pixels the auto-mask removed and which source frame won the minimum, and the range of the disparity at every scale -- the
+ * two places where a step that learns nothing (a stationary scene, a disparity collapsed to a constant) shows.  A read-only pass over
+ * all scales of a step at once: nscales (1..MDX_MAX_SCALES), B, H, W >= 1 with H * W < 2^32, S (1..MDX_MAX_SRC), automask (0 / 1);
+ * h, w: HOST arrays of nscales disparity sizes, each >= 1 and otherwise free; idx: HOST array of nscales device pointers to uint8
+ * [B,H,W] arg-min channels, always full resolution; disp: HOST array of nscales device pointers to contiguous float32
+ * [B,1,h[s],w[s]], 4-byte aligned.  An entry of idx or disp may be NULL: that half of the scale's records is 0 and says "absent".
+ *   mdx_loss_stats_plan      -> the number of blocks of pass 1 = the number of partial slots (>= 1; MDX_ERR_BAD_SHAPE when it does
+ *                            not fit an int); with blockmap (HOST, that many entries of mdx_loss_stats_blockmap_entry_bytes() = 16:
+ *                            int32 {scale, image, chunk, 0 = index map / 1 = disparity}) it writes the map the caller copies to the
+ *                            device once.  Scale after scale, image after image, per image ceil(H * W / mdx_loss_stats_index_chunk())
+ *                            index chunks, then ceil(h[s] * w[s] / mdx_loss_stats_disp_chunk()) disparity chunks; a NULL map keeps
+ *                            its slots.
+ *   mdx_loss_stats_partials  block b writes the record of its chunk to slot b of partials (DEVICE, nblocks slots of
+ *                            mdx_loss_stats_partial_bytes() = 72, 8-byte aligned); nblocks must be the plan's.  uint8 maps are read
+ *                            as 16-byte vectors and disparities as float4 where the IMAGE's base (idx[s] + b * H * W) is 16-byte
+ *                            aligned and the chunk is whole; element by element otherwise and in an image's tail.  An index
+ *                            >= (automask ? 2S : S) counts as bad_index and in no winner.  A disparity element is finite when its
+ *                            exponent bits are not all ones; it is added, and its square formed and added, in double; finite
+ *                            elements are compared by value (-0 below +0, denormals whatever the denormal mode).
+ *   mdx_loss_stats_finish    one block per scale, one of its four waves per image: adds each image's slots in a fixed order and
+ *                            writes records[s * B + b] (DEVICE, mdx_loss_stats_record_bytes() = 72 each, 8-byte aligned).  With
+ *                            history (DEVICE, nscales entries of mdx_loss_stats_history_bytes() = 152, 8-byte aligned, zeroed once
+ *                            by the caller; or NULL) it advances history[s] as the struct below says.  static_share in (0, 1].
+ * Refusals come before any HIP call: NULL pointers (the arrays, blockmap, partials, records), then shapes (a size out of range,
+ * H * W >= 2^32, static_share outside (0, 1] or not finite, nblocks < 1 or not the plan's), then alignment.  Every slot, record and
+ * history entry is written by exactly one thread with plain stores: no atomics, nothing to clear, the same inputs give the same
+ * bits at every launch, and the pair is capturable and replayable.  Nothing but the three outputs is written. */
+typedef struct mdx_loss_stats {            /* 72 bytes, per (scale, image) */
+    double disp_sum, disp_sumsq;           /* over FINITE disparity elements; float -> double, squares formed in double */
+    float disp_min, disp_max;              /* over finite elements, compared by value; 0 when there is none */
+    uint32_t winner[2 * MDX_MAX_SRC];      /* winner[c] = pixels with idx == c.  automask: c < S are the identity channels (masked
+                                              pixels), S <= c < 2S the warped sources; without automask c < S are the sources.
+                                              0 for every c that is not legal */
+    uint32_t bad_index;                    /* pixels with idx >= (automask ? 2S : S): a corrupt map */
+    uint32_t disp_nonfinite;               /* exponent bits all ones */
+    uint32_t index_present, disp_present;  /* 0: the pointer was NULL; that half's fields are 0 */
+} mdx_loss_stats;
+
+typedef struct mdx_loss_stats_history {    /* 152 bytes, per scale; all-zero is the valid initial state */
+    int64_t passes, images;                /* images += B per pass with an index map */
+    int64_t winner_total[2 * MDX_MAX_SRC]; /* sums of winner[] over passes and images */
+    int64_t bad_passes, first_bad_pass;    /* a pass with bad_index > 0 or disp_nonfinite > 0 in any image; 1-based, 0 = never */
+    int64_t static_images, first_static_pass, last_static_pass;
+                                           /* automask only: an image is static when (double)masked >= static_share * (double)(H*W),
+                                              masked = sum of winner[c < S] */
+    double max_masked_share;               /* automask only: (double)masked / (double)(H*W), largest over images and passes */
+    int64_t max_masked_pass;               /* that pass, the first of a tie; 0 = no masked pixel yet */
+    double min_disp_range;                 /* (double)disp_max - (double)disp_min of an image with at least one finite element,
+                                              smallest seen */
+    int64_t min_disp_range_pass;           /* that pass, the first of a tie; 0 = none yet */
+} mdx_loss_stats_history;
+
+size_t mdx_loss_stats_partial_bytes(void);
+size_t mdx_loss_stats_record_bytes(void);
+size_t mdx_loss_stats_history_bytes(void);
+size_t mdx_loss_stats_blockmap_entry_bytes(void);
+int mdx_loss_stats_index_chunk(void);
+int mdx_loss_stats_disp_chunk(void);
+int mdx_loss_stats_plan(int nscales, int B, int H, int W, const int *h, const int *w, void *blockmap);
+int mdx_loss_stats_partials(int nscales, int B, int H, int W, int S, int automask, const int *h, const int *w,
+                            const uint8_t *const *idx, const float *const *disp, const void *blockmap, int nblocks, void *partials,
+                            void *stream);
+int mdx_loss_stats_finish(int nscales, int B, int H, int W, int S, int automask, const int *h, const int *w, double static_share,
+                          const void *partials, void *records, void *history, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fine-grained ops behind the reference's model_layer / model_loss API (each differentiable)
  * ---------------------------------------------------------------------------------------- */
