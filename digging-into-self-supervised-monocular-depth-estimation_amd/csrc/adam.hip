@@ -7,7 +7,7 @@
 // fused_adam_utils.cuh's expression by expression, including where it is carried out in double (beta * moment, lr / bias
 // correction, + eps): the results agree with torch's kernel to the last bit wherever its compiler did not contract a
 // multiply-add, and to an ulp otherwise.
-#include "mdx_common.hpp"
+#include "mdx_multi_tensor.hpp"
 
 namespace mdx {
 
@@ -16,9 +16,6 @@ struct AdamTensor {
     const float *step;        // this tensor's step count (float32, already incremented for this step)
     long long n;
 };
-constexpr int ADAM_MAX_GRADS = 384;          // gradient pointers travel as kernel arguments (they change from step to step)
-struct AdamGrads { const float *g[ADAM_MAX_GRADS]; };
-constexpr int ADAM_CHUNK = 4096;             // elements per block: 256 threads x 4 float4
 
 __device__ __forceinline__ void adam_one(float &param, float grad, float &exp_avg, float &exp_avg_sq, double beta1, double beta2,
                                          double eps, float step_size, float bias_correction2_sqrt)
@@ -29,21 +26,10 @@ __device__ __forceinline__ void adam_one(float &param, float grad, float &exp_av
     param -= step_size * exp_avg / denom;
 }
 
-// The guard's device record (mdx_adam_guard_record_bytes()): written by guard_finish_kernel, read by adam_step_guarded_kernel and,
-// on request, by the host (mdx.optim.Adam.guard_stats).
-struct GuardRecord {
-    float total_norm;         // L2 norm of every gradient of the step: sum of squares in double, rounded once
-    float coef;               // min(1, max_grad_norm / (total_norm + 1e-6)) in float32; exactly 1 without a limit
-    int skipped;              // 1: total_norm was not finite and the step wrote nothing
-    int reserved;
-    long long steps;          // guarded steps so far, skipped ones included
-    long long skipped_steps;
-};
-
 // One block's work of the step.  GUARDED: the launch returns at once when the record says "skipped", and Adam consumes
 // grad * coef (one float32 multiply, rounded before Adam's own arithmetic); coef == 1.0f leaves every gradient its bits.
 template <bool GUARDED>
-__device__ __forceinline__ void adam_step_block(const AdamTensor *__restrict__ tab, const AdamGrads &grads, int first,
+__device__ __forceinline__ void adam_step_block(const AdamTensor *__restrict__ tab, const GradPointers &grads, int first,
                                                 const int2 *__restrict__ blockmap, const float *__restrict__ lr_ptr, double lr,
                                                 double beta1, double beta2, double eps, const GuardRecord *__restrict__ rec)
 {
@@ -61,10 +47,10 @@ __device__ __forceinline__ void adam_step_block(const AdamTensor *__restrict__ t
     const float bias_correction1 = (float)bc1, bias_correction2_sqrt = (float)sqrt(bc2);
     const double lr_double = lr_ptr ? (double)*lr_ptr : lr;
     const float step_size = (float)(lr_double / bias_correction1);
-    const long long base = (long long)bm.y * ADAM_CHUNK;
+    const long long base = (long long)bm.y * MT_CHUNK;
     const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)g) & 15) == 0);
 #pragma unroll
-    for (int k = 0; k < ADAM_CHUNK / (256 * 4); ++k) {
+    for (int k = 0; k < MT_CHUNK / (256 * 4); ++k) {
         const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
         if (i >= t.n) break;
         if (vec && i + 3 < t.n) {
@@ -88,7 +74,7 @@ __device__ __forceinline__ void adam_step_block(const AdamTensor *__restrict__ t
     }
 }
 
-__global__ __launch_bounds__(256) void adam_step_kernel(const AdamTensor *__restrict__ tab, AdamGrads grads, int first,
+__global__ __launch_bounds__(256) void adam_step_kernel(const AdamTensor *__restrict__ tab, GradPointers grads, int first,
                                                         const int2 *__restrict__ blockmap, const float *__restrict__ lr_ptr, double lr,
                                                         double beta1, double beta2, double eps)
 {
@@ -112,17 +98,17 @@ __device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
 
 // Same table, block map and gradient pointers as adam_step_kernel; partials[blockIdx.x] = the sum of g^2 over this block's chunk.
 // Squares and sums in double: 1e30 squared overflows float32 and must not read as non-finite.
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const AdamTensor *__restrict__ tab, AdamGrads grads, int first,
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const AdamTensor *__restrict__ tab, GradPointers grads, int first,
                                                          const int2 *__restrict__ blockmap, double *__restrict__ partials)
 {
     __shared__ double lds[4];
     const int2 bm = blockmap[blockIdx.x];
     const long long n = tab[first + bm.x].n;
     const float *__restrict__ g = grads.g[bm.x];
-    const long long base = (long long)bm.y * ADAM_CHUNK;
-    constexpr int K = ADAM_CHUNK / (256 * 4);
+    const long long base = (long long)bm.y * MT_CHUNK;
+    constexpr int K = MT_CHUNK / (256 * 4);
     double acc = 0.0;
-    if ((((uintptr_t)g) & 15) == 0 && base + ADAM_CHUNK <= n) {
+    if ((((uintptr_t)g) & 15) == 0 && base + MT_CHUNK <= n) {
         float4 G[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) G[k] = *reinterpret_cast<const float4 *>(g + base + ((long long)k * 256 + threadIdx.x) * 4);
@@ -170,7 +156,7 @@ __global__ __launch_bounds__(256) void guard_finish_kernel(const AdamTensor *__r
     for (int i = threadIdx.x; i < ntensors; i += 256) *const_cast<float *>(tab[i].step) += 1.0f;
 }
 
-__global__ __launch_bounds__(256) void adam_step_guarded_kernel(const AdamTensor *__restrict__ tab, AdamGrads grads, int first,
+__global__ __launch_bounds__(256) void adam_step_guarded_kernel(const AdamTensor *__restrict__ tab, GradPointers grads, int first,
                                                                 const int2 *__restrict__ blockmap, const float *__restrict__ lr_ptr,
                                                                 double lr, double beta1, double beta2, double eps,
                                                                 const GuardRecord *__restrict__ rec)
@@ -178,22 +164,12 @@ __global__ __launch_bounds__(256) void adam_step_guarded_kernel(const AdamTensor
     adam_step_block<true>(tab, grads, first, blockmap, lr_ptr, lr, beta1, beta2, eps, rec);
 }
 
-static int fill_grads(AdamGrads &G, const float *const *grads, int count)
-{
-    for (int i = 0; i < count; ++i) {
-        if (!grads[i]) return MDX_ERR_NULL_POINTER;
-        G.g[i] = grads[i];
-    }
-    for (int i = count; i < ADAM_MAX_GRADS; ++i) G.g[i] = nullptr;
-    return MDX_OK;
-}
-
 }  // namespace mdx
 
 using namespace mdx;
 
-MDX_EXPORT int mdx_adam_max_tensors(void) { return ADAM_MAX_GRADS; }
-MDX_EXPORT int mdx_adam_chunk(void) { return ADAM_CHUNK; }
+MDX_EXPORT int mdx_adam_max_tensors(void) { return MT_MAX_TENSORS; }
+MDX_EXPORT int mdx_adam_chunk(void) { return MT_CHUNK; }
 MDX_EXPORT size_t mdx_adam_table_entry_bytes(void) { return sizeof(AdamTensor); }
 
 // table: DEVICE array of {float *param, *exp_avg, *exp_avg_sq; const float *step; int64 numel} (mdx_adam_table_entry_bytes() each);
@@ -204,14 +180,10 @@ MDX_EXPORT size_t mdx_adam_table_entry_bytes(void) { return sizeof(AdamTensor); 
 MDX_EXPORT int mdx_adam_step(const void *table, int first, int count, const float *const *grads, const void *blockmap, int nblocks,
                              const float *lr_ptr, double lr, double beta1, double beta2, double eps, void *stream)
 {
-    if (!table || !grads || !blockmap) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > ADAM_MAX_GRADS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
-    AdamGrads G;
-    for (int i = 0; i < count; ++i) {
-        if (!grads[i]) return MDX_ERR_NULL_POINTER;
-        G.g[i] = grads[i];
-    }
-    for (int i = count; i < ADAM_MAX_GRADS; ++i) G.g[i] = nullptr;
+    if (!grads) return MDX_ERR_NULL_POINTER;
+    if (int rc = check_plan(table, first, count, blockmap, nblocks)) return rc;
+    GradPointers G;
+    if (int rc = fill_grads(G, grads, count, false)) return rc;
     hipLaunchKernelGGL(adam_step_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const AdamTensor *)table, G, first,
                        (const int2 *)blockmap, lr_ptr, lr, beta1, beta2, eps);
     return check_launch();
@@ -224,11 +196,11 @@ MDX_EXPORT size_t mdx_adam_guard_partials_bytes(int nblocks) { return nblocks < 
 MDX_EXPORT int mdx_adam_grad_sumsq(const void *table, int first, int count, const float *const *grads, const void *blockmap,
                                    int nblocks, double *partials, void *stream)
 {
-    if (!table || !grads || !blockmap || !partials) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > ADAM_MAX_GRADS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
+    if (!grads || !partials) return MDX_ERR_NULL_POINTER;
+    if (int rc = check_plan(table, first, count, blockmap, nblocks)) return rc;
     if (!aligned(partials, sizeof(double))) return MDX_ERR_MISALIGNED;
-    AdamGrads G;
-    if (int rc = fill_grads(G, grads, count)) return rc;
+    GradPointers G;
+    if (int rc = fill_grads(G, grads, count, false)) return rc;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const AdamTensor *)table, G, first,
                        (const int2 *)blockmap, partials);
     return check_launch();
@@ -249,11 +221,11 @@ MDX_EXPORT int mdx_adam_step_guarded(const void *table, int first, int count, co
                                      int nblocks, const float *lr_ptr, double lr, double beta1, double beta2, double eps,
                                      const void *record, void *stream)
 {
-    if (!table || !grads || !blockmap || !record) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > ADAM_MAX_GRADS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
+    if (!grads || !record) return MDX_ERR_NULL_POINTER;
+    if (int rc = check_plan(table, first, count, blockmap, nblocks)) return rc;
     if (!aligned(record, sizeof(long long))) return MDX_ERR_MISALIGNED;
-    AdamGrads G;
-    if (int rc = fill_grads(G, grads, count)) return rc;
+    GradPointers G;
+    if (int rc = fill_grads(G, grads, count, false)) return rc;
     hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const AdamTensor *)table, G, first,
                        (const int2 *)blockmap, lr_ptr, lr, beta1, beta2, eps, (const GuardRecord *)record);
     return check_launch();

@@ -12,7 +12,7 @@
 // block sums may arrive in any order (one vector global atomic per block) and the result has no tolerance.  The position enters
 // through i, so two exchanged elements change the digest.  i is taken modulo 2^32: a tensor of 2^32 words or more is not refused,
 // its words 2^32 apart merely share their index.
-#include "mdx_common.hpp"
+#include "mdx_multi_tensor.hpp"
 
 namespace mdx {
 
@@ -21,8 +21,6 @@ struct DigestTensor {
     long long n;
 };
 static_assert(sizeof(DigestTensor) == 16, "the digest's table entry is 16 bytes (include/mdx.h)");
-constexpr int DIGEST_MAX_TENSORS = 384;      // = mdx_adam_max_tensors(): one block-map recipe for the family
-constexpr int DIGEST_CHUNK = 4096;           // = mdx_adam_chunk()
 
 // A multiplicative spread of the index, then murmur3's 32-bit finaliser (include/mdx.h states the recipe).
 __device__ __forceinline__ unsigned long long digest_one(uint32_t i, uint32_t u)
@@ -42,10 +40,10 @@ __global__ __launch_bounds__(256) void digest_words_kernel(const DigestTensor *_
     __shared__ unsigned long long lds[4];
     const int2 bm = blockmap[blockIdx.x];                 // (tensor of this launch, chunk)
     const DigestTensor t = tab[first + bm.x];
-    const long long base = (long long)bm.y * DIGEST_CHUNK;
-    constexpr int K = DIGEST_CHUNK / (256 * 4);
+    const long long base = (long long)bm.y * MT_CHUNK;
+    constexpr int K = MT_CHUNK / (256 * 4);
     unsigned long long acc = 0;
-    if ((((uintptr_t)t.w) & 15) == 0 && base + DIGEST_CHUNK <= t.n) {      // a whole aligned chunk: every load in flight first
+    if ((((uintptr_t)t.w) & 15) == 0 && base + MT_CHUNK <= t.n) {      // a whole aligned chunk: every load in flight first
         uint4 U[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) U[k] = *reinterpret_cast<const uint4 *>(t.w + base + ((long long)k * 256 + threadIdx.x) * 4);
@@ -85,8 +83,8 @@ MDX_EXPORT size_t mdx_digest_table_entry_bytes(void) { return sizeof(DigestTenso
 MDX_EXPORT int mdx_digest_words(const void *table, int first, int count, const void *blockmap, int nblocks, uint64_t *out,
                                 void *stream)
 {
-    if (!table || !blockmap || !out) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > DIGEST_MAX_TENSORS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
+    if (!out) return MDX_ERR_NULL_POINTER;
+    if (int rc = check_plan(table, first, count, blockmap, nblocks)) return rc;
     if (!aligned(out, sizeof(uint64_t))) return MDX_ERR_MISALIGNED;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "atomicAdd's 64-bit type");
     // the entry point clears its own slice: the block sums are added into it, and a caller (or a replayed graph) never zeroes

@@ -8,7 +8,7 @@
 //   ema_update_kernel   shadow <- lerp(shadow, live, w), w = (float)(1 - d_t), ATen's lerp rule in float32; 12 B per element
 //   ema_tick_kernel     one thread, after the last update launch of one update: the counters (every launch saw the same t)
 //   ema_swap_kernel     live <-> shadow, bit for bit, in place: the weights' storage then holds the average
-#include "mdx_common.hpp"
+#include "mdx_multi_tensor.hpp"
 
 namespace mdx {
 
@@ -21,14 +21,6 @@ struct EmaRecord {            // mdx_ema_record_bytes(); zeroed once by the call
     long long updates;        // updates applied so far: t of the next one
     long long held;           // updates withheld because the guard skipped the step
 };
-struct EmaGuardRecord {       // adam.hip: GuardRecord (mdx_adam_guard_record_bytes()); only `skipped` is read here
-    float total_norm, coef;
-    int skipped, reserved;
-    long long steps, skipped_steps;
-};
-static_assert(sizeof(EmaGuardRecord) == 32, "the step guard's record is 32 bytes (include/mdx.h)");
-constexpr int EMA_MAX_TENSORS = 384;         // = mdx_adam_max_tensors(): one block-map recipe for both
-constexpr int EMA_CHUNK = 4096;              // = mdx_adam_chunk()
 
 // ATen's lerp (ATen/native/Lerp.h) with self = e, end = p: the form that is exact at the nearer end.
 __device__ __forceinline__ float ema_one(float e, float p, float w)
@@ -39,7 +31,7 @@ __device__ __forceinline__ float ema_one(float e, float p, float w)
 
 __global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor *__restrict__ tab, int first,
                                                          const int2 *__restrict__ blockmap, double decay, int warmup,
-                                                         const EmaRecord *__restrict__ rec, const EmaGuardRecord *__restrict__ guard)
+                                                         const EmaRecord *__restrict__ rec, const GuardRecord *__restrict__ guard)
 {
     if (guard && guard->skipped) return;
     const long long updates = rec->updates;               // ema_tick_kernel advances it behind the last launch of this update
@@ -51,10 +43,10 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor *__rest
     const float w = (float)(1.0 - d);
     const int2 bm = blockmap[blockIdx.x];                 // (tensor of this launch, chunk)
     const EmaTensor t = tab[first + bm.x];
-    const long long base = (long long)bm.y * EMA_CHUNK;
+    const long long base = (long long)bm.y * MT_CHUNK;
     const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.e) & 15) == 0);
-    constexpr int K = EMA_CHUNK / (256 * 4);
-    if (vec && base + EMA_CHUNK <= t.n) {                 // a whole chunk: every load in flight before the first store
+    constexpr int K = MT_CHUNK / (256 * 4);
+    if (vec && base + MT_CHUNK <= t.n) {                 // a whole chunk: every load in flight before the first store
         float4 P[K], E[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -91,7 +83,7 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor *__rest
     }
 }
 
-__global__ __launch_bounds__(1) void ema_tick_kernel(EmaRecord *__restrict__ rec, const EmaGuardRecord *__restrict__ guard)
+__global__ __launch_bounds__(1) void ema_tick_kernel(EmaRecord *__restrict__ rec, const GuardRecord *__restrict__ guard)
 {
     if (guard && guard->skipped) rec->held += 1;
     else rec->updates += 1;
@@ -103,10 +95,10 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(const EmaTensor *__restri
     const int2 bm = blockmap[blockIdx.x];
     const EmaTensor t = tab[first + bm.x];
     unsigned int *p = reinterpret_cast<unsigned int *>(t.p), *e = reinterpret_cast<unsigned int *>(t.e);
-    const long long base = (long long)bm.y * EMA_CHUNK;
+    const long long base = (long long)bm.y * MT_CHUNK;
     const bool vec = ((((uintptr_t)p | (uintptr_t)e) & 15) == 0);
 #pragma unroll
-    for (int k = 0; k < EMA_CHUNK / (256 * 4); ++k) {
+    for (int k = 0; k < MT_CHUNK / (256 * 4); ++k) {
         const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
         if (i >= t.n) break;
         if (vec && i + 3 < t.n) {
@@ -121,13 +113,6 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(const EmaTensor *__restri
             }
         }
     }
-}
-
-static int check_plan(const void *table, int first, int count, const void *blockmap, int nblocks)
-{
-    if (!table || !blockmap) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > EMA_MAX_TENSORS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
-    return MDX_OK;
 }
 
 }  // namespace mdx
@@ -145,7 +130,7 @@ MDX_EXPORT int mdx_ema_update(const void *table, int first, int count, const voi
     if (!(decay >= 0.0 && decay < 1.0)) return MDX_ERR_BAD_SHAPE;                    // a NaN fails both comparisons
     if (!aligned(record, sizeof(long long)) || (guard_record && !aligned(guard_record, sizeof(long long)))) return MDX_ERR_MISALIGNED;
     hipLaunchKernelGGL(ema_update_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const EmaTensor *)table, first,
-                       (const int2 *)blockmap, decay, warmup ? 1 : 0, (const EmaRecord *)record, (const EmaGuardRecord *)guard_record);
+                       (const int2 *)blockmap, decay, warmup ? 1 : 0, (const EmaRecord *)record, (const GuardRecord *)guard_record);
     return check_launch();
 }
 
@@ -154,7 +139,7 @@ MDX_EXPORT int mdx_ema_tick(void *record, const void *guard_record, void *stream
     if (!record) return MDX_ERR_NULL_POINTER;
     if (!aligned(record, sizeof(long long)) || (guard_record && !aligned(guard_record, sizeof(long long)))) return MDX_ERR_MISALIGNED;
     hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (EmaRecord *)record,
-                       (const EmaGuardRecord *)guard_record);
+                       (const GuardRecord *)guard_record);
     return check_launch();
 }
 

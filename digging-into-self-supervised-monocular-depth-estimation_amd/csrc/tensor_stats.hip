@@ -11,7 +11,7 @@
 // that tensor's slots in a fixed order.  No atomics and nothing to clear -- every slot, record and history entry the pass owns is
 // overwritten (or advanced) by exactly one thread -- so the same inputs give the same bits at every launch and a replayed graph has
 // no state of its own (LABNOTES, "hipMemsetAsync inside a captured graph").
-#include "mdx_common.hpp"
+#include "mdx_multi_tensor.hpp"
 
 namespace mdx {
 
@@ -20,9 +20,6 @@ struct StatsTensor {
     long long n;
 };
 static_assert(sizeof(StatsTensor) == 16, "the statistics' table entry is 16 bytes (include/mdx.h)");
-constexpr int STATS_MAX_TENSORS = 384;       // = mdx_adam_max_tensors(): one block-map recipe for the family
-constexpr int STATS_CHUNK = 4096;            // = mdx_adam_chunk()
-struct StatsGrads { const float *g[STATS_MAX_TENSORS]; };      // restated from adam.hip (AdamGrads); here an entry may be NULL
 
 // One record: a tensor's (mdx_tensor_stats) and, with the same fields over one chunk, a block's partial.
 struct StatsRecord {
@@ -109,17 +106,17 @@ __device__ __forceinline__ void stats_store(StatsRecord *__restrict__ out, const
 
 // Pass 1.  Block b of the launch: chunk bm.y of tensor first + bm.x -> partials[b].  A NULL gradient pointer (a parameter that
 // received no gradient this step): the weight half alone, and the partial says "gradient absent".
-__global__ __launch_bounds__(256) void tensor_stats_partials_kernel(const StatsTensor *__restrict__ tab, StatsGrads grads, int first,
+__global__ __launch_bounds__(256) void tensor_stats_partials_kernel(const StatsTensor *__restrict__ tab, GradPointers grads, int first,
                                                                     const int2 *__restrict__ blockmap, StatsRecord *__restrict__ partials)
 {
     __shared__ StatsLds lds;
     const int2 bm = blockmap[blockIdx.x];                 // (tensor of this launch, chunk)
     const StatsTensor t = tab[first + bm.x];
     const float *__restrict__ g = grads.g[bm.x];
-    const long long base = (long long)bm.y * STATS_CHUNK;
-    constexpr int K = STATS_CHUNK / (256 * 4);
+    const long long base = (long long)bm.y * MT_CHUNK;
+    constexpr int K = MT_CHUNK / (256 * 4);
     StatsAcc a;
-    if (((((uintptr_t)t.w) | ((uintptr_t)g)) & 15) == 0 && base + STATS_CHUNK <= t.n) {     // whole and aligned: every load in flight first
+    if (((((uintptr_t)t.w) | ((uintptr_t)g)) & 15) == 0 && base + MT_CHUNK <= t.n) {     // whole and aligned: every load in flight first
         float4 W[K], G[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) W[k] = *reinterpret_cast<const float4 *>(t.w + base + ((long long)k * 256 + threadIdx.x) * 4);
@@ -194,12 +191,11 @@ MDX_EXPORT size_t mdx_tensor_stats_history_bytes(void) { return sizeof(mdx_tenso
 MDX_EXPORT int mdx_tensor_stats_partials(const void *table, int first, int count, const float *const *grads, const void *blockmap,
                                          int nblocks, void *partials, void *stream)
 {
-    if (!table || !grads || !blockmap || !partials) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > STATS_MAX_TENSORS || nblocks < 1) return MDX_ERR_BAD_SHAPE;
+    if (!grads || !partials) return MDX_ERR_NULL_POINTER;
+    if (int rc = check_plan(table, first, count, blockmap, nblocks)) return rc;
     if (!aligned(partials, sizeof(double))) return MDX_ERR_MISALIGNED;
-    StatsGrads G;
-    for (int i = 0; i < count; ++i) G.g[i] = grads[i];                  // NULL: no gradient for this tensor in this pass
-    for (int i = count; i < STATS_MAX_TENSORS; ++i) G.g[i] = nullptr;
+    GradPointers G;
+    fill_grads(G, grads, count, true);                                  // NULL: no gradient for this tensor in this pass
     hipLaunchKernelGGL(tensor_stats_partials_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (const StatsTensor *)table, G,
                        first, (const int2 *)blockmap, (StatsRecord *)partials);
     return check_launch();
@@ -209,7 +205,7 @@ MDX_EXPORT int mdx_tensor_stats_finish(int first, int count, const int *offsets,
                                        void *stream)
 {
     if (!offsets || !partials || !records) return MDX_ERR_NULL_POINTER;
-    if (first < 0 || count < 1 || count > STATS_MAX_TENSORS) return MDX_ERR_BAD_SHAPE;
+    if (first < 0 || count < 1 || count > MT_MAX_TENSORS) return MDX_ERR_BAD_SHAPE;
     if (!aligned(partials, sizeof(double)) || !aligned(records, sizeof(double)) || !aligned(history, sizeof(double)))
         return MDX_ERR_MISALIGNED;
     hipLaunchKernelGGL(tensor_stats_finish_kernel, dim3(count), dim3(256), 0, (hipStream_t)stream, first, offsets,

@@ -167,6 +167,23 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _capturing():
+    """True while the current HIP stream is being captured into a graph."""
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def host_tensor(structs, dtype=torch.uint8):
+    """The bytes of a ctypes structure or array as a host tensor of its own (a copy)."""
+    return torch.frombuffer(bytearray(bytes(structs)), dtype=dtype).clone()
+
+
+def read_structs(who, buf, struct_type, count):
+    """`buf` (a tensor, read on the host: synchronises) as `count` ctypes structures; `who` names the caller in the refusal."""
+    if _capturing():
+        raise MdxError("%s() synchronises and the current stream is being captured" % who)
+    return (struct_type * count).from_buffer_copy(buf.cpu().numpy().tobytes())
+
+
 def workspace(nbytes, device):
     """A scratch buffer of at least `nbytes` (what an mdx_*_workspace_bytes() returned) for one launch: uint8, so hand it over
     as ptr(ws, torch.uint8).  Whole 16-byte units and never empty; the base is aligned to 16 bytes and more, as every

@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import api, stream
+from ._lib import _capturing, api, host_tensor, read_structs, stream
 
 BINS = 2 * _lib.MAX_SRC
 
@@ -29,10 +29,6 @@ class LossStatsHistory(C.Structure):       # include/mdx.h: mdx_loss_stats_histo
 
 
 RECORD_WORDS, HISTORY_WORDS = C.sizeof(LossStatsRecord) // 8, C.sizeof(LossStatsHistory) // 8
-
-
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 class LossStats(object):
@@ -177,8 +173,8 @@ class LossStats(object):
             for b in range(B):
                 recs[s * B + b] = self._torch_record(None if i is None else i[b], None if d is None else d[b])
             self._advance(hist[s], [recs[s * B + b] for b in range(B)], self.scales_hw[s][0] * self.scales_hw[s][1])
-        self._records.copy_(torch.frombuffer(bytearray(bytes(recs)), dtype=torch.int64).view(n * B, RECORD_WORDS))
-        self._history.copy_(torch.frombuffer(bytearray(bytes(hist)), dtype=torch.int64).view(n, HISTORY_WORDS))
+        self._records.copy_(host_tensor(recs, torch.int64).view(n * B, RECORD_WORDS))
+        self._history.copy_(host_tensor(hist, torch.int64).view(n, HISTORY_WORDS))
 
     # ---- the pass ---------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -205,15 +201,10 @@ class LossStats(object):
                                   self._partials.data_ptr(), self._records.data_ptr(), self._history.data_ptr(), st)
         return self._records
 
-    def _read(self, what, buf, struct_type, count):
-        if _capturing():
-            raise _lib.MdxError("mdx.loss_stats.LossStats.%s() synchronises and the current stream is being captured" % what)
-        return (struct_type * count).from_buffer_copy(buf.cpu().numpy().tobytes())
-
     def records(self):
         """The records of the last pass as ctypes structures, [scale][image].  Synchronises."""
         n, B = len(self.scales_hw), self.B
-        recs = self._read("records", self._records, LossStatsRecord, n * B)
+        recs = read_structs("mdx.loss_stats.LossStats.records", self._records, LossStatsRecord, n * B)
         return [[recs[s * B + b] for b in range(B)] for s in range(n)]
 
     def host(self):
@@ -243,7 +234,7 @@ class LossStats(object):
         are 1-based, 0 is "never"), and from them `masked_share` and `shares` over all images of all passes.  Synchronises."""
         pixels = self.H * self.W
         out = []
-        for h in self._read("history", self._history, LossStatsHistory, len(self.scales_hw)):
+        for h in read_structs("mdx.loss_stats.LossStats.history", self._history, LossStatsHistory, len(self.scales_hw)):
             total = h.images * pixels
             masked = sum(h.winner_total[c] for c in range(self.S)) if self.automask else 0
             out.append(dict(passes=h.passes, images=h.images, winner_total=list(h.winner_total), bad_passes=h.bad_passes,

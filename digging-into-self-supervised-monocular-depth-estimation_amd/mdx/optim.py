@@ -25,12 +25,70 @@ for finding the layer behind a skipped or clipped step."""
 import contextlib
 import ctypes as C
 import math
-import struct
 
 import torch
 
 from . import _lib
-from ._lib import api, stream
+from ._lib import _capturing, api, host_tensor, read_structs, stream
+
+
+# ---- what the four passes share (csrc/mdx_multi_tensor.hpp): a PLAN is a device table, the launches over it, a pointer key --------
+def _device_table(entry_type, entry_bytes, *tensor_lists):
+    """The device table of a plan: entry i holds the pointers of the i-th tensor of every list, then the first list's numel."""
+    assert C.sizeof(entry_type) == entry_bytes
+    host = (entry_type * len(tensor_lists[0]))()
+    for i, ts in enumerate(zip(*tensor_lists)):
+        host[i] = entry_type(*[t.data_ptr() for t in ts], ts[0].numel())
+    return host_tensor(host).to(tensor_lists[0][0].device)
+
+
+def _launches(tensors, base):
+    """[(first table entry, count, block map, blocks)] covering `tensors`, whose table entries start at `base`."""
+    chunk, per = api.mdx_adam_chunk(), api.mdx_adam_max_tensors()
+    launches = []
+    for first in range(0, len(tensors), per):
+        count = min(per, len(tensors) - first)
+        bm = []
+        for t in range(count):
+            bm += [(t, c) for c in range((tensors[first + t].numel() + chunk - 1) // chunk)]
+        blockmap = torch.tensor(bm, dtype=torch.int32).to(tensors[0].device)
+        launches.append((base + first, count, blockmap, len(bm)))
+    return launches
+
+
+def _key(*tensor_lists):
+    """A plan is good for as long as every tensor stays where it is."""
+    return tuple(t.data_ptr() for ts in tensor_lists for t in ts)
+
+
+def _check_device(who, dev):
+    if dev.index != torch.cuda.current_device():
+        raise _lib.MdxError("mdx.optim.%s live on %s but the current device is cuda:%d" % (who, dev, torch.cuda.current_device()))
+
+
+def _check_storage(who, tensors, key):
+    if _key(tensors) != key:
+        raise _lib.MdxError("mdx.optim.%s changed its storage since construction" % who)
+
+
+def _dense_f32(t, dev, like=None):
+    """What the kernels walk: float32 on the GPU `dev`, contiguous or channels-last -- or, per gradient of a step (one call, no
+    second look at the strides), laid out as `like`, a tensor that is."""
+    return (t.is_cuda and t.device == dev and t.dtype == torch.float32 and not t.is_sparse
+            and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last) if like is None
+                 else t.stride() == like.stride() and t.shape == like.shape))
+
+
+def _same_layout(a, b):
+    return a.stride() == b.stride() and a.shape == b.shape
+
+
+def _lr_args(group):
+    """(lr_ptr, lr) of a launch: a float32 device tensor travels as its pointer (a captured step's learning rate), else a double."""
+    lr = group["lr"]
+    if torch.is_tensor(lr) and lr.is_cuda and lr.dtype == torch.float32:
+        return lr.data_ptr(), 0.0
+    return None, float(lr)
 
 
 class _Table(C.Structure):
@@ -58,64 +116,38 @@ class Adam(torch.optim.Adam):
         return self.max_grad_norm is not None or self.skip_nonfinite
 
     # -- what one launch needs, built once per parameter group -------------------------------------------------------------
-    def _plan(self, gi, params, exp_avgs, exp_avg_sqs, steps):
-        key = tuple(t.data_ptr() for ts in (params, exp_avgs, exp_avg_sqs, steps) for t in ts)
+    # Two kinds of plan, each built in the first step that needs it and rebuilt when its pointer key changes: the plain step has
+    # one table per parameter group, the guarded step ONE table over the tensors of every group (the norm is global).
+    def _plan(self, gi, *lists):
+        """The plain step's plan for group gi; lists: params, exp_avgs, exp_avg_sqs, steps."""
+        key = _key(*lists)
         plan = self._plans.get(gi)
-        if plan is not None and plan["key"] == key:
-            return plan
-        plan = dict(key=key, table=self._table(params, exp_avgs, exp_avg_sqs, steps), launches=self._launches(params, 0))
-        self._plans[gi] = plan
+        if plan is None or plan["key"] != key:
+            plan = self._plans[gi] = dict(key=key, table=_device_table(_Table, api.mdx_adam_table_entry_bytes(), *lists),
+                                          launches=_launches(lists[0], 0))
         return plan
-
-    @staticmethod
-    def _table(params, exp_avgs, exp_avg_sqs, steps):
-        assert C.sizeof(_Table) == api.mdx_adam_table_entry_bytes()
-        host = (_Table * len(params))()
-        for i, (p, m, v, s) in enumerate(zip(params, exp_avgs, exp_avg_sqs, steps)):
-            host[i] = _Table(p.data_ptr(), m.data_ptr(), v.data_ptr(), s.data_ptr(), p.numel())
-        raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone()
-        return raw.to(params[0].device)
-
-    @staticmethod
-    def _launches(params, base):
-        """[(first table entry, count, block map, blocks)] covering `params`, whose table entries start at `base`."""
-        chunk, per = api.mdx_adam_chunk(), api.mdx_adam_max_tensors()
-        launches = []
-        for first in range(0, len(params), per):
-            count = min(per, len(params) - first)
-            bm = []
-            for t in range(count):
-                bm += [(t, c) for c in range((params[first + t].numel() + chunk - 1) // chunk)]
-            blockmap = torch.tensor(bm, dtype=torch.int32).to(params[0].device)
-            launches.append((base + first, count, blockmap, len(bm)))
-        return launches
 
     def _guard_plan(self, todo):
-        """The guarded step's plan: ONE table over the tensors of every group (the norm is global), each group's launches with
-        their slice of the partials buffer, the record.  Built in the first (eager, warm-up) step, never inside a capture."""
-        key = tuple(t.data_ptr() for _, _, params, _, exp_avgs, exp_avg_sqs, steps in todo
-                    for ts in (params, exp_avgs, exp_avg_sqs, steps) for t in ts)
-        plan = self._guard
-        if plan is not None and plan["key"] == key:
-            return plan
-        dev = todo[0][2][0].device
-        cat = [sum((list(item[k]) for item in todo), []) for k in (2, 4, 5, 6)]
+        """The guarded step's plan: the table, each group's launches with their slice of the partials buffer, the record.  Built
+        in the first (eager, warm-up) step, never inside a capture."""
+        cat = [sum((list(item[k]) for item in todo), []) for k in (2, 4, 5, 6)]        # params, exp_avgs, exp_avg_sqs, steps
+        key = _key(*cat)
+        if self._guard is not None and self._guard["key"] == key:
+            return self._guard
+        dev = cat[0][0].device
         launches, base, slot = [], 0, 0
-        for ti, (_, _, params, _, _, _, _) in enumerate(todo):
-            for first, count, blockmap, nblocks in self._launches(params, base):
+        for ti, item in enumerate(todo):
+            for first, count, blockmap, nblocks in _launches(item[2], base):
                 launches.append((ti, first, first - base, count, blockmap, nblocks, slot))
                 slot += nblocks
-            base += len(params)
+            base += len(item[2])
         if self._record is None or self._record.device != dev:
-            self._record = torch.zeros(api.mdx_adam_guard_record_bytes() // 8, dtype=torch.int64, device=dev)
+            assert C.sizeof(GuardRecord) == api.mdx_adam_guard_record_bytes()
+            self._record = torch.zeros(C.sizeof(GuardRecord) // 8, dtype=torch.int64, device=dev)
         partials = torch.empty(api.mdx_adam_guard_partials_bytes(slot) // 8, dtype=torch.float64, device=dev)
-        plan = dict(key=key, table=self._table(*cat), launches=launches, partials=partials, ntensors=base, nblocks=slot)
-        self._guard = plan
-        return plan
-
-    @staticmethod
-    def _dense(a, b):
-        return a.stride() == b.stride() and a.shape == b.shape
+        self._guard = dict(key=key, table=_device_table(_Table, api.mdx_adam_table_entry_bytes(), *cat), launches=launches,
+                           partials=partials, ntensors=base, nblocks=slot)
+        return self._guard
 
     def _native_ok(self, group, params, grads, exp_avgs, exp_avg_sqs, steps):
         if not self.native or group["weight_decay"] != 0 or group["amsgrad"] or group["maximize"] or group.get("differentiable"):
@@ -123,13 +155,9 @@ class Adam(torch.optim.Adam):
         if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
             return False
         dev = params[0].device
-        for p, g, m, v, s in zip(params, grads, exp_avgs, exp_avg_sqs, steps):
-            if not (p.is_cuda and p.device == dev and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
-                    and (p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last))
-                    and self._dense(g, p) and self._dense(m, p) and self._dense(v, p)
-                    and torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and s.numel() == 1):
-                return False
-        return True
+        return all(_dense_f32(p, dev) and _dense_f32(g, dev, p) and _same_layout(m, p) and _same_layout(v, p)
+                   and torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and s.numel() == 1
+                   for p, g, m, v, s in zip(params, grads, exp_avgs, exp_avg_sqs, steps))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -154,30 +182,22 @@ class Adam(torch.optim.Adam):
                 return self._torch_guarded_step()
             return self._native_guarded_step(todo)
         for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps in todo:
-            if params[0].device.index != torch.cuda.current_device():
-                raise _lib.MdxError("mdx.optim.Adam: parameters live on %s but the current device is cuda:%d"
-                                    % (params[0].device, torch.cuda.current_device()))
+            _check_device("Adam: parameters", params[0].device)
             plan = self._plan(gi, params, exp_avgs, exp_avg_sqs, steps)
             torch._foreach_add_(steps, 1)
-            lr = group["lr"]
-            lr_ptr = lr.data_ptr() if torch.is_tensor(lr) else None
-            if torch.is_tensor(lr) and not (lr.is_cuda and lr.dtype == torch.float32):
-                lr, lr_ptr = float(lr), None
+            lr_ptr, lr = _lr_args(group)
             beta1, beta2 = group["betas"]
             for first, count, blockmap, nblocks in plan["launches"]:
                 garr = (C.c_void_p * count)(*[g.data_ptr() for g in grads[first:first + count]])
-                api.mdx_adam_step(plan["table"].data_ptr(), first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr,
-                                  0.0 if lr_ptr is not None else float(lr), beta1, beta2, group["eps"], stream())
+                api.mdx_adam_step(plan["table"].data_ptr(), first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr, lr,
+                                  beta1, beta2, group["eps"], stream())
         return None
 
     # -- the guarded step ---------------------------------------------------------------------------------------------------
     def _native_guarded_step(self, todo):
         """Sum of squares (one launch per <= mdx_adam_max_tensors() tensors), finish (norm, coefficient, skip flag, totals, step
         counts), guarded Adam: include/mdx.h.  Nothing here looks at a value on the host."""
-        dev = todo[0][2][0].device
-        if dev.index != torch.cuda.current_device():
-            raise _lib.MdxError("mdx.optim.Adam: parameters live on %s but the current device is cuda:%d"
-                                % (dev, torch.cuda.current_device()))
+        _check_device("Adam: parameters", todo[0][2][0].device)
         plan = self._guard_plan(todo)
         table, partials, record = plan["table"].data_ptr(), plan["partials"].data_ptr(), self._record.data_ptr()
         garrs = []
@@ -189,13 +209,10 @@ class Adam(torch.optim.Adam):
                                   int(self.skip_nonfinite), record, stream())
         for garr, (ti, first, local, count, blockmap, nblocks, slot) in zip(garrs, plan["launches"]):
             group = todo[ti][1]
-            lr = group["lr"]
-            lr_ptr = lr.data_ptr() if torch.is_tensor(lr) else None
-            if torch.is_tensor(lr) and not (lr.is_cuda and lr.dtype == torch.float32):
-                lr, lr_ptr = float(lr), None
+            lr_ptr, lr = _lr_args(group)
             beta1, beta2 = group["betas"]
-            api.mdx_adam_step_guarded(table, first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr,
-                                      0.0 if lr_ptr is not None else float(lr), beta1, beta2, group["eps"], record, stream())
+            api.mdx_adam_step_guarded(table, first, count, garr, blockmap.data_ptr(), nblocks, lr_ptr, lr, beta1, beta2,
+                                      group["eps"], record, stream())
         self._last_native = True
         return None
 
@@ -227,12 +244,24 @@ class Adam(torch.optim.Adam):
         the one place of the guard that synchronises."""
         out = dict(self._host_stats)
         if self._record is not None:
-            norm, coef, skipped, _, steps, skipped_steps = struct.unpack("<ffiiqq", self._record.cpu().numpy().tobytes())
+            rec = GuardRecord.from_buffer_copy(self._record.cpu().numpy().tobytes())
             if self._last_native:
-                out.update(total_norm=norm, coef=coef, skipped=bool(skipped))
-            out["steps"] += steps
-            out["skipped_steps"] += skipped_steps
+                out.update(total_norm=rec.total_norm, coef=rec.coef, skipped=bool(rec.skipped))
+            out["steps"] += rec.steps
+            out["skipped_steps"] += rec.skipped_steps
         return out
+
+    def guard_decision(self, device):
+        """What a follower of the last step needs to withhold its own work with a skipped step (WeightEMA.update): (pointer of the
+        device record, False) when that step took the native path and the follower's kernels run on the record's `device` (None:
+        it runs on the host); else (None, was the step skipped?) -- the host's flag or, for a native step, ONE synchronising read."""
+        if not self.guarded or (self._last_native and self._record is None):
+            return None, False
+        if not self._last_native:
+            return None, self._host_stats["skipped"]
+        if device == self._record.device:
+            return self._record.data_ptr(), False
+        return None, self.guard_stats()["skipped"]
 
     def guard_snapshot(self):
         """The guard's record and totals, for a caller that undoes steps (model_train.graphed_step's warm-up)."""
@@ -303,33 +332,19 @@ class WeightEMA(object):
         self._native = self._native_ok()
         self._record = self._table = self._launches = None
         if self._native:
-            dev = self.live[0].device
-            assert C.sizeof(_EmaTable) == api.mdx_ema_table_entry_bytes() and api.mdx_ema_record_bytes() == 16
-            host = (_EmaTable * len(self.live))()
-            for i, (t, e) in enumerate(zip(self.live, self.shadow)):
-                host[i] = _EmaTable(t.data_ptr(), e.data_ptr(), t.numel())
-            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
-            self._launches = Adam._launches(self.live, 0)
-            self._record = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._key = tuple(t.data_ptr() for t in self.live)
+            assert api.mdx_ema_record_bytes() == 16
+            self._table = _device_table(_EmaTable, api.mdx_ema_table_entry_bytes(), self.live, self.shadow)
+            self._launches = _launches(self.live, 0)
+            self._record = torch.zeros(2, dtype=torch.int64, device=self.live[0].device)
+            self._key = _key(self.live)
 
     def _native_ok(self):
-        if not self.native:
-            return False
         dev = self.live[0].device
-        for t, e in zip(self.live, self.shadow):
-            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.numel() > 0
-                    and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) and Adam._dense(e, t)):
-                return False
-        return True
+        return self.native and all(_dense_f32(t, dev) and t.numel() > 0 and _same_layout(e, t) for t, e in zip(self.live, self.shadow))
 
     def _check_native(self):
-        dev = self.live[0].device
-        if dev.index != torch.cuda.current_device():
-            raise _lib.MdxError("mdx.optim.WeightEMA: tensors live on %s but the current device is cuda:%d"
-                                % (dev, torch.cuda.current_device()))
-        if tuple(t.data_ptr() for t in self.live) != self._key:
-            raise _lib.MdxError("mdx.optim.WeightEMA: a parameter or buffer has changed its storage since construction")
+        _check_device("WeightEMA: tensors", self.live[0].device)
+        _check_storage("WeightEMA: a parameter or buffer has", self.live, self._key)
 
     def _weight(self, t):
         d = min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
@@ -340,17 +355,11 @@ class WeightEMA(object):
         """One update, after `optimizer.step()`.  A guarded mdx.optim.Adam hands its device record over when its last step took the
         native path; where the guard decided on the host (torch's own step), so does the skip here."""
         guard = None
-        if optimizer is not None and getattr(optimizer, "guarded", False):
-            if not optimizer._last_native:
-                if optimizer._host_stats["skipped"]:
-                    self._host["held"] += 1
-                    return
-            elif optimizer._record is not None:
-                if self._native and optimizer._record.device == self.live[0].device:
-                    guard = optimizer._record.data_ptr()
-                elif optimizer.guard_stats()["skipped"]:              # torch-path average of a native optimiser: read it
-                    self._host["held"] += 1
-                    return
+        if getattr(optimizer, "guarded", False):
+            guard, skipped = optimizer.guard_decision(self.live[0].device if self._native else None)
+            if skipped:
+                self._host["held"] += 1
+                return
         if not self._native:
             w = self._weight(self._host["updates"])
             for e, t in zip(self.shadow, self.live):
@@ -439,10 +448,6 @@ class _DigestTable(C.Structure):
     _fields_ = [("w", C.c_void_p), ("n", C.c_int64)]
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 class WeightDigest(object):
     """One 64-bit digest per tensor of `tensors`, for equality only: what data-parallel ranks compare after a step
     (model_tool.parallel.check_replicas) and what a checkpoint's state file records of the weight files beside it
@@ -474,15 +479,10 @@ class WeightDigest(object):
         self._native = self._native_ok()
         self._table = self._launches = None
         if self._native:
-            dev = self.tensors[0].device
-            assert C.sizeof(_DigestTable) == api.mdx_digest_table_entry_bytes()
-            host = (_DigestTable * len(self.tensors))()
-            for i, t in enumerate(self.tensors):
-                host[i] = _DigestTable(t.data_ptr(), t.numel())
-            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
-            self._launches = Adam._launches(self.tensors, 0)
-            self._out = torch.zeros(len(self.tensors), dtype=torch.int64, device=dev)
-            self._key = tuple(t.data_ptr() for t in self.tensors)
+            self._table = _device_table(_DigestTable, api.mdx_digest_table_entry_bytes(), self.tensors)
+            self._launches = _launches(self.tensors, 0)
+            self._out = torch.zeros(len(self.tensors), dtype=torch.int64, device=self.tensors[0].device)
+            self._key = _key(self.tensors)
         else:
             self._out = torch.zeros(len(self.tensors), dtype=torch.int64)
 
@@ -497,19 +497,8 @@ class WeightDigest(object):
         return True
 
     def _native_ok(self):
-        if not self.native:
-            return False
         dev = self.tensors[0].device
-        return all(t.is_cuda and t.device == dev and t.numel() > 0
-                   and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) for t in self.tensors)
-
-    def _check_native(self):
-        dev = self.tensors[0].device
-        if dev.index != torch.cuda.current_device():
-            raise _lib.MdxError("mdx.optim.WeightDigest: tensors live on %s but the current device is cuda:%d"
-                                % (dev, torch.cuda.current_device()))
-        if tuple(t.data_ptr() for t in self.tensors) != self._key:
-            raise _lib.MdxError("mdx.optim.WeightDigest: a tensor has changed its storage since construction")
+        return self.native and all(_dense_f32(t, dev) and t.numel() > 0 for t in self.tensors)
 
     @staticmethod
     def _numpy_digest(t):
@@ -535,7 +524,8 @@ class WeightDigest(object):
                 raise _lib.MdxError("mdx.optim.WeightDigest: the numpy path reads the tensors on the host and cannot be captured")
             self._out.copy_(torch.tensor([self._numpy_digest(t) for t in self.tensors], dtype=torch.int64))
             return self._out
-        self._check_native()
+        _check_device("WeightDigest: tensors", self.tensors[0].device)
+        _check_storage("WeightDigest: a tensor has", self.tensors, self._key)
         for first, count, blockmap, nblocks in self._launches:
             api.mdx_digest_words(self._table.data_ptr(), first, count, blockmap.data_ptr(), nblocks, self._out.data_ptr(), stream())
         return self._out
@@ -549,6 +539,11 @@ class WeightDigest(object):
 
 class _StatsTable(C.Structure):
     _fields_ = [("w", C.c_void_p), ("n", C.c_int64)]
+
+
+class GuardRecord(C.Structure):            # csrc/mdx_multi_tensor.hpp: GuardRecord (mdx_adam_guard_record_bytes())
+    _fields_ = [("total_norm", C.c_float), ("coef", C.c_float), ("skipped", C.c_int), ("reserved", C.c_int),
+                ("steps", C.c_int64), ("skipped_steps", C.c_int64)]
 
 
 class TensorStats(C.Structure):            # include/mdx.h: mdx_tensor_stats
@@ -601,12 +596,8 @@ class GradStats(object):
         self._records = torch.zeros(n, 5, dtype=torch.int64, device=dev)
         self._history = torch.zeros(n, 7, dtype=torch.int64, device=dev)
         if self._native:
-            assert (api.mdx_tensor_stats_table_entry_bytes(), api.mdx_tensor_stats_partial_bytes(), api.mdx_tensor_stats_record_bytes(),
-                    api.mdx_tensor_stats_history_bytes()) == (C.sizeof(_StatsTable), 40, 40, 56)
-            host = (_StatsTable * n)()
-            for i, t in enumerate(self.tensors):
-                host[i] = _StatsTable(t.data_ptr(), t.numel())
-            self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).clone().to(dev)
+            assert (api.mdx_tensor_stats_partial_bytes(), api.mdx_tensor_stats_record_bytes(), api.mdx_tensor_stats_history_bytes()) == (40, 40, 56)
+            self._table = _device_table(_StatsTable, api.mdx_tensor_stats_table_entry_bytes(), self.tensors)
             chunk = api.mdx_adam_chunk()
             offsets = [0]
             for t in self.tensors:
@@ -616,29 +607,17 @@ class GradStats(object):
             self._offsets = torch.tensor(offsets, dtype=torch.int32).to(dev)
             # each launch with the slot its slice of the partials starts at and its own host array of gradient pointers
             self._launches = [(first, count, blockmap, nblocks, offsets[first], (C.c_void_p * count)())
-                              for first, count, blockmap, nblocks in Adam._launches(self.tensors, 0)]
+                              for first, count, blockmap, nblocks in _launches(self.tensors, 0)]
             self._partials = torch.empty(offsets[-1], 5, dtype=torch.int64, device=dev)
-            self._key = tuple(t.data_ptr() for t in self.tensors)
+            self._key = _key(self.tensors)
 
     def _native_ok(self):
-        if not self.native:
-            return False
         dev = self.tensors[0].device
-        return all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.numel() > 0 and not t.is_sparse
-                   and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)) for t in self.tensors)
+        return self.native and all(_dense_f32(t, dev) and t.numel() > 0 for t in self.tensors)
 
     def _grads_native(self, grads):
         dev = self.tensors[0].device
-        return all(g is None or (g.is_cuda and g.device == dev and g.dtype == torch.float32 and not g.is_sparse and Adam._dense(g, t))
-                   for g, t in zip(grads, self.tensors))
-
-    def _check_native(self):
-        dev = self.tensors[0].device
-        if dev.index != torch.cuda.current_device():
-            raise _lib.MdxError("mdx.optim.GradStats: parameters live on %s but the current device is cuda:%d"
-                                % (dev, torch.cuda.current_device()))
-        if tuple(t.data_ptr() for t in self.tensors) != self._key:
-            raise _lib.MdxError("mdx.optim.GradStats: a parameter has changed its storage since construction")
+        return all(g is None or _dense_f32(g, dev, t) for g, t in zip(grads, self.tensors))
 
     @staticmethod
     def _torch_record(w, g):
@@ -669,8 +648,8 @@ class GradStats(object):
                 h.first_bad_weight_pass = h.first_bad_weight_pass or h.passes
             if r.grad_present and r.grad_sumsq > h.max_grad_sumsq:
                 h.max_grad_sumsq, h.max_grad_pass = r.grad_sumsq, h.passes
-        self._records.copy_(torch.frombuffer(bytearray(bytes(recs)), dtype=torch.int64).view(n, 5))
-        self._history.copy_(torch.frombuffer(bytearray(bytes(hist)), dtype=torch.int64).view(n, 7))
+        self._records.copy_(host_tensor(recs, torch.int64).view(n, 5))
+        self._history.copy_(host_tensor(hist, torch.int64).view(n, 7))
 
     @torch.no_grad()
     def compute(self, grads=None):
@@ -684,7 +663,8 @@ class GradStats(object):
         if not self._last_native:
             self._torch_compute(grads)
             return self._records
-        self._check_native()
+        _check_device("GradStats: parameters", self.tensors[0].device)
+        _check_storage("GradStats: a parameter has", self.tensors, self._key)
         table, partials, s = self._table.data_ptr(), self._partials.data_ptr(), stream()
         for first, count, blockmap, nblocks, slot, garr in self._launches:
             for i in range(count):
@@ -697,9 +677,7 @@ class GradStats(object):
         return self._records
 
     def _read(self, what, buf, struct_type):
-        if _capturing():
-            raise _lib.MdxError("mdx.optim.GradStats.%s() synchronises and the current stream is being captured" % what)
-        return (struct_type * len(self.tensors)).from_buffer_copy(buf.cpu().numpy().tobytes())
+        return read_structs("mdx.optim.GradStats." + what, buf, struct_type, len(self.tensors))
 
     def host(self):
         """{name: {grad_norm, weight_norm, grad_absmax, weight_absmax, grad_nonfinite, weight_nonfinite, grad_zeros, grad_present,

@@ -44,6 +44,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from mdx._lib import _capturing as capturing       # True while the current HIP stream is being captured into a graph
+
 
 def dp_graph_allowed(world):
     """May the step of a `world`-rank job be captured into ONE hipGraph, exchange included?  (If not, a captured step takes the
@@ -55,11 +57,6 @@ def dp_graph_allowed(world):
     data-parallel step is the split capture (model_train.trainer.train_step with opt.graph, the default); the eager step with
     32 MB buckets overlapping backward is what runs without a capture.  tools/scale_check.sh holds the runs that settle it."""
     return int(world) <= 1 or os.environ.get("MDX_DP_GRAPH", "") == "1"
-
-
-def capturing():
-    """True while the current HIP stream is being captured into a graph."""
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 def _refuse_under_capture(what):

@@ -70,11 +70,25 @@ def _struct_fields(source, name):
 
 
 def test_the_guard_record_is_read_as_adam_writes_it():
-    """ema.hip restates adam.hip's GuardRecord (adam.hip stays as it is, so the struct cannot move to a shared header) and reads
-    `skipped` from it: the two declarations agree field by field, so a reordering over there fails here, not on the GPU."""
-    theirs, ours = _struct_fields("adam.hip", "GuardRecord"), _struct_fields("ema.hip", "EmaGuardRecord")
-    assert theirs == ours == [("float", "total_norm"), ("float", "coef"), ("int", "skipped"), ("int", "reserved"),
-                              ("long long", "steps"), ("long long", "skipped_steps")]      # include/mdx.h: skipped at byte 8
+    """adam.hip writes the guard's record and ema.hip reads `skipped` from it through ONE declaration (csrc/mdx_multi_tensor.hpp),
+    which Python restates as a ctypes structure: the two agree field by field and offset by offset, so a reordering over there
+    fails here, not on the GPU."""
+    from mdx.optim import GuardRecord
+    theirs = _struct_fields("mdx_multi_tensor.hpp", "GuardRecord")
+    assert theirs == [("float", "total_norm"), ("float", "coef"), ("int", "skipped"), ("int", "reserved"),
+                      ("long long", "steps"), ("long long", "skipped_steps")]
+    ctype = {"float": C.c_float, "int": C.c_int, "long long": C.c_int64}
+    assert C.sizeof(C.c_longlong) == 8
+    assert [(ctype[kind], name) for kind, name in theirs] == [(t, n) for n, t in GuardRecord._fields_]      # names, order, types
+    offset = 0
+    for kind, name in theirs:                               # every field naturally aligned: the C layout has no padding
+        assert getattr(GuardRecord, name).offset == offset and offset % C.sizeof(ctype[kind]) == 0, name
+        offset += C.sizeof(ctype[kind])
+    assert offset == C.sizeof(GuardRecord) == _lib.lib().mdx_adam_guard_record_bytes() == 32
+    assert GuardRecord.skipped.offset == 8                  # include/mdx.h: skipped at byte 8
+    for source in ("ema.hip", "adam.hip"):                  # no record struct of their own
+        text = open(os.path.join(ROOT, PKG, "csrc", source)).read()
+        assert not re.search(r"\bstruct\s+\w*GuardRecord\b", text) and '#include "mdx_multi_tensor.hpp"' in text, source
 
 
 def _update(table=FAKE, first=0, count=2, blockmap=FAKE, nblocks=3, decay=0.999, warmup=1, record=FAKE, guard=None):

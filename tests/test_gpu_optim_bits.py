@@ -10,7 +10,11 @@ The set holds the smallest shapes at which the work split (4096 elements per blo
 The second half holds the same runs to what a graph capture would see of them -- which entry points are called with which slice of
 which plan, and how many allocations each step makes -- against literals recorded by this file's code on the build of commit
 73278bc (LABNOTES.md, same section: the second attempt).  A rearrangement that is meant to leave a captured step alone has to meet
-both halves."""
+both halves.
+
+The third part does the same for the fourth member of the family, mdx.optim.GradStats over the same 392 parameters with a pass after
+every step: the bits of its records and history, its entry-point calls and its allocations, against literals recorded by this
+file's code on the build of commit 604b610 (LABNOTES.md, same section: the third attempt)."""
 import hashlib
 import importlib
 
@@ -57,9 +61,10 @@ def _allocations():
 
 def _run(variant, watch=None):
     """{name: value} of one variant: "a" unguarded, "b" max_grad_norm=1.0 + skip_nonfinite, "c" = b + a WeightEMA updated after every
-    step and exchanged twice at the end.  `watch` (a dict): receives "allocated", the allocations made inside each step (the
-    optimiser's and the average's, not the gradients'), and "params"."""
-    from mdx.optim import Adam, WeightEMA
+    step and exchanged twice at the end, "d" = b + a GradStats over every parameter with a pass after every step.  `watch` (a dict):
+    receives "allocated", the allocations made inside each step (the optimiser's and the average's, not the gradients'), "params",
+    and for "d" the allocations of the statistics' constructor and of each pass."""
+    from mdx.optim import Adam, GradStats, WeightEMA
     gen = torch.Generator().manual_seed(20240519)
     shapes = GROUP0 + GROUP1
     params = [torch.nn.Parameter(_place(torch.randn(s, generator=gen), i == OFFSET_ONE)) for i, s in enumerate(shapes)]
@@ -71,6 +76,11 @@ def _run(variant, watch=None):
     ema = WeightEMA(holder, decay=0.999, warmup=True) if variant == "c" else None
     if ema is not None:
         assert ema._native and len(ema._launches) == 2
+    before = _allocations()
+    stats = GradStats(params) if variant == "d" else None
+    if stats is not None:
+        assert stats._native and len(stats._launches) == 2
+        watch["stats_built"] = _allocations() - before
     for step in range(1, STEPS + 1):
         for i, p in enumerate(params):
             scale = 10.0 ** float(torch.randint(-3, 3, (1,), generator=gen))
@@ -86,6 +96,11 @@ def _run(variant, watch=None):
         if watch is not None:
             watch.setdefault("allocated", []).append(_allocations() - before)
             watch["params"] = params
+        if stats is not None:
+            before = _allocations()
+            stats.compute()
+            assert stats._last_native
+            watch.setdefault("stats_allocated", []).append(_allocations() - before)
     h = hashlib.sha256()
     for p in params:
         st = optimizer.state[p]
@@ -108,6 +123,11 @@ def _run(variant, watch=None):
         for e in ema.shadow:
             h.update(e.detach().cpu().numpy().tobytes())
         out["ema"] = ema.stats()
+    if stats is not None:
+        hs = hashlib.sha256()
+        for t in (stats._records, stats._history):
+            hs.update(t.cpu().numpy().tobytes())
+        out["stats"] = hs.hexdigest()
     out["sha256"] = h.hexdigest()
     return out
 
@@ -134,7 +154,8 @@ def test_the_bits_are_those_recorded(variant):
 # commit 73278bc.  A step that rebuilds no plan allocates nothing; step 1 creates Adam's state and the first plans; steps 4 and 5
 # rebuild (one parameter loses its gradient and has it again).
 _ARGS = {"mdx_adam_step": (1, 2, 5), "mdx_adam_grad_sumsq": (1, 2, 5), "mdx_adam_step_guarded": (1, 2, 5), "mdx_adam_guard_finish": (None, 1, 3),
-         "mdx_ema_update": (1, 2, 4), "mdx_ema_swap": (1, 2, 4), "mdx_ema_tick": (None, None, None), "mdx_digest_words": (1, 2, 4)}
+         "mdx_ema_update": (1, 2, 4), "mdx_ema_swap": (1, 2, 4), "mdx_ema_tick": (None, None, None), "mdx_digest_words": (1, 2, 4),
+         "mdx_tensor_stats_partials": (1, 2, 5), "mdx_tensor_stats_finish": (0, 1, None)}
 
 
 class _Recorder(object):
@@ -204,3 +225,24 @@ def test_the_calls_and_allocations_are_those_recorded(variant, monkeypatch):
     got = _observe(variant, monkeypatch)
     print(variant, got)
     assert got == SEEN[variant]
+
+
+# ---- the fourth member: the per-tensor statistics over the same parameters ----------------------------------------------------------
+# Variant "d" is "b" with a GradStats pass after every step (the `inf` of step 2 and the absent gradient of step 4 included).  The
+# digest covers the record and history buffers after step 5.  The pass's plan is built in the constructor and does not depend on
+# which gradients are present: the same two partial launches and two finish launches (no block map: 0) at every pass.
+# Allocations: records, history, table, slot offsets, two block maps and the partials in the constructor; none in any pass.
+_STATS_PASS = _named("tensor_stats_partials", [(0, 384, 385), (384, 8, 9)]) + _named("tensor_stats_finish", [(0, 384, 0), (384, 8, 0)])
+STATS_SEEN = {"guard": _GUARD, "sha256": RECORDED["b"]["sha256"], "stats": "daaa0a56a0870cf1799310b77e7e6316440733c856436e7ed7518a22c89e8df9",
+              "calls": STEPS * _STATS_PASS, "built": 7, "allocated": [0] * STEPS}
+
+
+def test_the_statistics_pass_is_that_recorded(monkeypatch):
+    import mdx.optim
+    rec, watch = _Recorder(mdx.optim.api), {}
+    monkeypatch.setattr(mdx.optim, "api", rec)
+    got = _run("d", watch)
+    got.update(calls=[c for c in rec.calls if c[0].startswith("tensor_stats")], built=watch["stats_built"],
+               allocated=watch["stats_allocated"])
+    print("d", got)
+    assert got == STATS_SEEN

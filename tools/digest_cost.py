@@ -51,12 +51,12 @@ def kernels(reps, rounds, out):
     import torch
     tr, _ = _trainer(False, 1)
     from mdx._lib import api, stream
-    from mdx.optim import Adam
+    from mdx.optim import _Table, _device_table
     digest = tr.setting.optim["digest"]
     ts = digest.tensors
     n = sum(t.numel() for t in ts)
     # grad_sumsq over the weights themselves: its table is read for numel only, the "gradients" are the same pointers the digest reads
-    table = Adam._table(ts, ts, ts, ts)
+    table = _device_table(_Table, api.mdx_adam_table_entry_bytes(), ts, ts, ts, ts)
     launches = digest._launches
     partials = torch.empty(sum(nb for _, _, _, nb in launches), dtype=torch.float64, device=ts[0].device)
     garrs = [(C.c_void_p * count)(*[t.data_ptr() for t in ts[first:first + count]]) for first, count, _, _ in launches]

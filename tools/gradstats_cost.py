@@ -58,7 +58,7 @@ def kernels(reps, rounds, out):
     import torch
     tr, inputs = _trainer(False, 1)
     from mdx._lib import api, stream
-    from mdx.optim import Adam, GradStats
+    from mdx.optim import GradStats, _Table, _device_table, _launches
     tr.train_step(dict(inputs))                             # one eager step: .grad holds its gradients
     pairs = [(p.detach(), p.grad) for p in tr.setting.parameters if p.grad is not None]      # the same tensors in every column
     ws, gs = [w for w, _ in pairs], [g for _, g in pairs]
@@ -66,8 +66,8 @@ def kernels(reps, rounds, out):
     stats = GradStats(ws)
     stats.compute(gs)
     assert stats._last_native
-    table = Adam._table(ws, ws, ws, ws)                     # grad_sumsq reads the table for numel only
-    launches = Adam._launches(ws, 0)
+    table = _device_table(_Table, api.mdx_adam_table_entry_bytes(), ws, ws, ws, ws)      # grad_sumsq reads the table for numel only
+    launches = _launches(ws, 0)
     partials = torch.empty(2 * sum(nb for _, _, _, nb in launches), dtype=torch.float64, device=ws[0].device)
     garrs = [[(C.c_void_p * count)(*[t.data_ptr() for t in ts[first:first + count]]) for first, count, _, _ in launches] for ts in (gs, ws)]
 
