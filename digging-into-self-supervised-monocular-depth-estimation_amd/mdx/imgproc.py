@@ -9,6 +9,9 @@ to Pillow's output divided by 255.
 
     batch keys consumed:  ("depth_idx", 0) int32 [B, n] / ("depth_val", 0) float32 [B, n]: sparse velodyne ground truth
                           (padding: index h*w) + "depth_hw" [B, 2], CPU  ->  ("depth", 0) [B,1,h,w]
+                          or, with --gpu_velodyne, the scans: ("velo", 0) float32 [B, nmax, 3] (points with x >= 0, padded) +
+                          "velo_n" [B], "velo_P" float64 [B,3,4], "velo_hw" int32 [B,2] (native h, w), "velo_gt" int32 [B,2]
+                          (the map's size), CPU  ->  ("depth", 0) [B,1,gh,gw] through velodyne_depth
                           ("raw", f)  uint8 [B, hmax, wmax, 3]      "raw_size" int32 [B, 2] (h, w), CPU
                           "raw_flip"  bool [B], CPU                  "raw_jitter" float64 [B, 9], CPU:
                                                                        (enabled, order[4], brightness, contrast,
@@ -35,7 +38,9 @@ RESAMPLE_JOB = np.dtype([("src", "<u8"), ("xbounds", "<u8"), ("xkk", "<u8"), ("y
 JITTER_JOB = np.dtype([("src", "<u8"), ("dst_f32", "<u8"), ("dst_u8", "<u8"), ("lsum", "<u8"),
                        ("h", "<i4"), ("w", "<i4"), ("order", "<i4", (4,)), ("hue_shift", "<i4"),
                        ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4")])
-assert RESAMPLE_JOB.itemsize == 112 and JITTER_JOB.itemsize == 72
+VELODYNE_JOB = np.dtype([("points", "<u8"), ("out", "<u8"), ("P", "<f8", (12,)), ("n", "<i4"), ("stride", "<i4"),
+                         ("h", "<i4"), ("w", "<i4"), ("gh", "<i4"), ("gw", "<i4"), ("vel_depth", "<i4"), ("flip", "<i4")])
+assert RESAMPLE_JOB.itemsize == 112 and JITTER_JOB.itemsize == 72 and VELODYNE_JOB.itemsize == 144
 
 
 def _check_u8(t, what):
@@ -214,6 +219,48 @@ def to_tensor(src_u8):
     return dst
 
 
+def velodyne_depth(points, counts, P, sizes, out_hw, flips=None, vel_depth=False):
+    """model_utility.point2depth -> resize_nearest -> np.fliplr -> float32 for a batch of velodyne scans (csrc/velodyne.hip;
+    the semantics: include/mdx.h, mdx_velodyne_depth) -> float32 [B, 1, gh, gw] on the points' device, 0 = no return.
+    points: float32 [B, nmax, 3 | 4] on the GPU, scan b in its first counts[b] rows, in file order (the other rows are never
+    read; a fourth column neither).  Host values: counts [B]; P [B, 3, 4] float64 and sizes [B] of (h, w), what
+    model_utility.velodyne_projection returns; out_hw = (gh, gw); flips [B] bool or None.  B = 0 and nmax = 0 are allowed."""
+    if not (torch.is_tensor(points) and points.is_cuda):
+        raise _lib.MdxError("velodyne_depth: the points must be a GPU tensor (there is no CPU form: model_utility.point2depth)")
+    if points.dtype != torch.float32 or points.dim() != 3 or points.shape[2] not in (3, 4) or not points.is_contiguous():
+        raise _lib.MdxError("velodyne_depth: contiguous float32 [B, nmax, 3 or 4] expected, got %s %s contiguous=%s"
+                            % (points.dtype, tuple(points.shape), points.is_contiguous()))
+    B, nmax, stride = (int(v) for v in points.shape)
+    gh, gw = int(out_hw[0]), int(out_hw[1])
+    if gh < 1 or gw < 1:
+        raise _lib.MdxError("velodyne_depth: empty output size %s" % (tuple(out_hw),))
+    dev = points.device
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64)).reshape(-1, 12)
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    flips = np.zeros(B, np.int32) if flips is None else np.asarray([int(bool(f)) for f in flips], np.int32)
+    if not (len(counts) == len(P) == len(sizes) == len(flips) == B):
+        raise _lib.MdxError("velodyne_depth: counts, P, sizes and flips must have one entry per scan (%d)" % B)
+    if B and (counts.min() < 0 or counts.max() > nmax):
+        raise _lib.MdxError("velodyne_depth: counts %s outside 0..%d" % (counts.tolist(), nmax))
+    out = torch.empty(B, 1, gh, gw, dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    base = _lib.ptr(points).value or 0           # (an empty tensor has no address: its scans hold no points)
+    jobs = np.zeros(B, VELODYNE_JOB)
+    idx = np.arange(B, dtype=np.uint64)
+    jobs["points"] = base + idx * np.uint64(4 * nmax * stride)
+    jobs["out"] = _lib.ptr(out).value + idx * np.uint64(4 * gh * gw)
+    jobs["P"], jobs["n"], jobs["stride"] = P, counts, stride
+    jobs["h"], jobs["w"], jobs["gh"], jobs["gw"] = sizes[:, 0], sizes[:, 1], gh, gw
+    jobs["vel_depth"], jobs["flip"] = int(bool(vel_depth)), flips
+    nbytes = _lib.api.mdx_velodyne_workspace_bytes(B, int(counts.max()), int(sizes[:, 0].max()), int(sizes[:, 1].max()))
+    ws = _lib.workspace(nbytes, dev)
+    _lib.api.mdx_velodyne_depth(jobs.ctypes.data, B, _lib.ptr(ws, torch.uint8), ws.numel(), _lib.stream())
+    ws.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
 def jitter_params(row):
     """one row of the batch's "raw_jitter" -> color_jitter's params entry (None when the sample is not jittered)."""
     row = [float(x) for x in row]
@@ -240,8 +287,18 @@ class image_prep(object):
         flips = [bool(v) for v in batch["raw_flip"].tolist()]
         params = [jitter_params(row) for row in batch["raw_jitter"].tolist()]
         any_jitter = any(p is not None for p in params)
-        drop = ("raw_size", "raw_flip", "raw_jitter", "depth_hw", ("depth_idx", 0), ("depth_val", 0))
+        drop = ("raw_size", "raw_flip", "raw_jitter", "depth_hw", ("depth_idx", 0), ("depth_val", 0),
+                ("velo", 0), "velo_n", "velo_P", "velo_hw", "velo_gt")
         out = {k: v for k, v in batch.items() if not (isinstance(k, tuple) and k[0] == "raw") and k not in drop}
+        if ("velo", 0) in batch:          # the scans themselves (KITTIDataset gpu_velo): projected here, csrc/velodyne.hip
+            gt = batch["velo_gt"].tolist()
+            if any(row != gt[0] for row in gt):
+                raise _lib.MdxError("image_prep: the ground-truth maps of a batch must share one size, got %s" % (sorted(set(map(tuple, gt))),))
+            pts = batch[("velo", 0)]
+            pts = pts if pts.is_cuda else pts.to(self.device, non_blocking=True)
+            out[("depth", 0)] = velodyne_depth(pts, batch["velo_n"].tolist(), batch["velo_P"].numpy(), batch["velo_hw"].tolist(),
+                                               gt[0], flips)
+            pts.record_stream(torch.cuda.current_stream(pts.device))
         if ("depth_idx", 0) in batch:     # sparse velodyne ground truth -> the dense [B,1,h,w] map the loader's contract names
             hw = batch["depth_hw"].tolist()
             if any(row != hw[0] for row in hw):     # the sparse indices of every sample address ONE [gh, gw] grid

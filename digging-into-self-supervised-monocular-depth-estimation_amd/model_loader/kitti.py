@@ -20,7 +20,7 @@ import torch
 from PIL import Image, ImageEnhance
 from torch.utils.data import Dataset
 
-from model_utility import point2depth, resize_nearest
+from model_utility import point2depth, resize_nearest, velodyne_projection
 
 SIDE_MAP = {"2": 2, "3": 3, "l": 2, "r": 3}
 K_NORM = np.array([[0.58, 0, 0.5, 0], [0, 1.92, 0.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float32)
@@ -70,10 +70,17 @@ def collate_raw(samples, keep=None):
     [B, hmax, wmax, 3] block per frame; `keep(key)` filters the other entries (processor.step_reads)."""
     from torch.utils.data import default_collate
     raw_keys = [k for k in samples[0] if isinstance(k, tuple) and k[0] == "raw"]
-    ragged = [k for k in samples[0] if isinstance(k, tuple) and k[0] in ("depth_idx", "depth_val")]
+    ragged = [k for k in samples[0] if isinstance(k, tuple) and k[0] in ("depth_idx", "depth_val", "velo")]
     rest = default_collate([{k: v for k, v in s.items() if k not in raw_keys and k not in ragged and (keep is None or keep(k))}
                             for s in samples])
-    if ragged:   # sparse ground truth: padded to the longest list; padding points one past the last pixel, value 0
+    if ("velo", 0) in ragged:   # gpu_velo: the scans, padded to the longest; "velo_n" says how many rows of each are points
+        n = max(int(s[("velo", 0)].shape[0]) for s in samples)
+        block = _batch_block((len(samples), n, 3), torch.float32)     # (the padding rows are never read: left as they are)
+        for i, s in enumerate(samples):
+            block[i, : s[("velo", 0)].shape[0]] = s[("velo", 0)]
+        rest[("velo", 0)] = block
+        rest["velo_n"] = torch.tensor([int(s[("velo", 0)].shape[0]) for s in samples], dtype=torch.int32)
+    if ("depth_idx", 0) in ragged:   # sparse ground truth: padded to the longest list; padding points one past the last pixel, value 0
         n = max(int(s[("depth_idx", 0)].numel()) for s in samples)
         hw = [int(s["depth_hw"][0]) * int(s["depth_hw"][1]) for s in samples]
         idx = torch.stack([torch.nn.functional.pad(s[("depth_idx", 0)], (0, n - s[("depth_idx", 0)].numel()), value=hw[i])
@@ -118,7 +125,8 @@ def _batch_block(shape, dtype):
 
 class KITTIDataset(Dataset):
     def __init__(self, datapath, filename, is_training, frame_ids, height=192, width=640, ext=".jpg", scale=4,
-                 k_mode="reference_mono", gt_size=(375, 1242), load_depth=True, uint8=False, gpu_prep=False):
+                 k_mode="reference_mono", gt_size=(375, 1242), load_depth=True, uint8=False, gpu_prep=False,
+                 gpu_velo=False):
         if height % 32 != 0 or width % 32 != 0:
             raise ValueError("(H, W) must be multiples of 32; KITTI sizes are (192, 640) or (320, 1024)")
         self.datapath, self.filename, self.is_training = datapath, list(filename), is_training
@@ -129,6 +137,10 @@ class KITTIDataset(Dataset):
         # gpu_prep: the worker only decodes; flip, the Lanczos pyramid, the jitter and ToTensor run on the GPU
         # (mdx.imgproc.image_prep, bit-equal to the Pillow calls below)
         self.gpu_prep = gpu_prep
+        # gpu_velo (with gpu_prep): the worker hands the scan's points over instead of the ground-truth map; image_prep projects
+        # them (mdx.imgproc.velodyne_depth, bit-equal to load_point below).  A day's calibration is parsed once per worker.
+        self.gpu_velo = gpu_velo
+        self._velo_calib = {}
 
     def __len__(self):
         return len(self.filename)
@@ -150,6 +162,19 @@ class KITTIDataset(Dataset):
         if do_flip:
             depth = np.fliplr(depth)
         return torch.from_numpy(np.ascontiguousarray(depth[None], dtype=np.float32))
+
+    def load_scan(self, folder, frame_index, side):
+        """what load_point projects, unprojected: the points point2depth keeps after its x >= 0 filter, float32 [n, 3] in file
+        order, with the projection matrix and native image size of (the day's calibration, camera) -- parsed once."""
+        calib_path = os.path.join(self.datapath, folder.split("/")[0])
+        key = (calib_path, SIDE_MAP[side])
+        if key not in self._velo_calib:
+            P, hw = velodyne_projection(calib_path, SIDE_MAP[side])
+            self._velo_calib[key] = (torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64)),
+                                     torch.from_numpy(np.ascontiguousarray(hw[:2], dtype=np.int32)))
+        velo = os.path.join(self.datapath, folder, "velodyne_points/data/{:010d}.bin".format(int(frame_index)))
+        points = np.fromfile(velo, dtype=np.float32).reshape(-1, 4)
+        return (torch.from_numpy(points[points[:, 0] >= 0, :3]),) + self._velo_calib[key]
 
     def intrinsics(self, scale):
         K = K_NORM.copy()
@@ -189,7 +214,10 @@ class KITTIDataset(Dataset):
             out["raw_size"] = torch.tensor([h, w], dtype=torch.int32)
             out["raw_flip"] = torch.tensor(bool(do_flip))
             out["raw_jitter"] = torch.tensor(jitter_row(jitter if do_color else None), dtype=torch.float64)
-        if self.load_depth:
+        if self.load_depth and self.gpu_prep and self.gpu_velo:
+            out[("velo", 0)], out["velo_P"], out["velo_hw"] = self.load_scan(folder, key_frame, side)
+            out["velo_gt"] = torch.tensor(self.gt_size, dtype=torch.int32)
+        elif self.load_depth:
             depth = self.load_point(folder, key_frame, side, do_flip)
             if self.gpu_prep:
                 # 95 % of a velodyne map is empty: hand over (pixel index, value) pairs -- 0.2 MB instead of 1.9 MB per

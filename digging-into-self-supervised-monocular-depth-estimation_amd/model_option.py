@@ -53,6 +53,12 @@ def options(argv=None):
     p.add_argument("--gpu_image_prep", type=str, default="auto", choices=["auto", "true", "false"],
                    help="KITTI loaders: workers only decode; flip, Lanczos pyramid, colour jitter and ToTensor run on the GPU "
                         "(bit-equal to Pillow; csrc/imgproc.hip).  auto = on when training on a GPU")
+    p.add_argument("--gpu_velodyne", type=int, default=0, choices=[0, 1],
+                   help="KITTI loaders, honoured only with gpu_image_prep on: the workers hand the velodyne scans over and the ground-truth "
+                        "map is projected on the GPU (bit-equal to point2depth; csrc/velodyne.hip).  Off by default.  Measured "
+                        "(tools/velodyne_cost.py, profiles/r13_velodyne_*, LABNOTES 'Velodyne ground truth'): ~75 us per batch of 12 on "
+                        "the GPU against ~27 us for the scatter it replaces; one worker's time per sample 7.2 -> 5.7 ms; no measurable "
+                        "gain in loader samples/s with 24 workers")
     p.add_argument("--synthetic_raw", action="store_true",
                    help="synthetic dataset hands over KITTI-sized decoded frames (1242x375 uint8), as the KITTI loaders do with gpu_image_prep")
     p.add_argument("--resume", type=int, default=0,

@@ -79,6 +79,8 @@ class setting(object):
             dataset = cls(opt.datapath, names, is_training, opt.frame_ids, opt.height, opt.width, ".jpg", len(opt.scales))
             dataset.uint8 = _opt(opt, "uint8_loader", False)
             dataset.gpu_prep = gpu_image_prep(opt, self.device)
+            # --gpu_velodyne (off by default, honoured only with the GPU image preparation): the workers hand the scans over
+            dataset.gpu_velo = dataset.gpu_prep and bool(int(_opt(opt, "gpu_velodyne", 0) or 0))
         sampler = None
         if self.distributed:
             sampler = DistributedSampler(dataset, self.world_size, self.rank, shuffle=shuffle, drop_last=True)

@@ -43,7 +43,9 @@ def step_reads(key):
     return True                                             # ("depth", 0), injected test entries
 
 
-HOST_KEYS = ("raw_size", "raw_flip", "raw_jitter", "depth_hw")     # read on the host by mdx.imgproc.image_prep: never uploaded
+# read on the host by mdx.imgproc.image_prep: never uploaded (velo_*: --gpu_velodyne; the scan itself, ("velo", 0), is a device key
+# like ("depth_idx", 0): step_reads keeps every tuple it does not name)
+HOST_KEYS = ("raw_size", "raw_flip", "raw_jitter", "depth_hw", "velo_n", "velo_P", "velo_hw", "velo_gt")
 
 
 def device_key(key):

@@ -49,9 +49,9 @@ def read_velodyne_points(filename):
     return points
 
 
-def point2depth(calib_path, point_path, cam=2, vel_depth=False):
-    """Projects a velodyne scan into camera `cam` -> sparse depth map [h, w] (model_utility.py:128-197).
-    Where several points fall on one pixel the nearest one wins -- with the reference's own index arithmetic, see below."""
+def velodyne_projection(calib_path, cam=2):
+    """The calibration half of point2depth: (P_velo2im float64 [3,4] = P_rect @ R_cam2rect @ velo2cam, im_shape int32 (h, w) from
+    S_rect_02) of a day's two calibration files.  point2depth calls it; mdx.imgproc.velodyne_depth takes exactly these values."""
     cam2cam = read_calib(os.path.join(calib_path, "calib_cam_to_cam.txt"))
     velo2cam = read_calib(os.path.join(calib_path, "calib_velo_to_cam.txt"))
     velo2cam = np.hstack((velo2cam["R"].reshape(3, 3), velo2cam["T"][..., np.newaxis]))
@@ -60,7 +60,13 @@ def point2depth(calib_path, point_path, cam=2, vel_depth=False):
     R_cam2rect = np.eye(4)
     R_cam2rect[:3, :3] = cam2cam["R_rect_00"].reshape(3, 3)
     P_rect = cam2cam["P_rect_0" + str(cam)].reshape(3, 4)
-    P_velo2im = P_rect @ R_cam2rect @ velo2cam
+    return P_rect @ R_cam2rect @ velo2cam, im_shape
+
+
+def point2depth(calib_path, point_path, cam=2, vel_depth=False):
+    """Projects a velodyne scan into camera `cam` -> sparse depth map [h, w] (model_utility.py:128-197).
+    Where several points fall on one pixel the nearest one wins -- with the reference's own index arithmetic, see below."""
+    P_velo2im, im_shape = velodyne_projection(calib_path, cam)
     velo = read_velodyne_points(point_path)
     velo = velo[velo[:, 0] >= 0, :]
     pts = (P_velo2im @ velo.T).T

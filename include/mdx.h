@@ -702,6 +702,39 @@ int mdx_color_convert_u8(int mode, const uint8_t *src, uint8_t *dst, size_t npix
  * src: n bytes, any layout; dst: n floats, 16-byte aligned. */
 int mdx_to_tensor_u8(const uint8_t *src, float *dst, size_t n, void *stream);
 
+/* ---- velodyne ground truth on the GPU   model_utility.point2depth (reference model_utility.py:128-197) -> resize_nearest
+ * -> np.fliplr -> float32, for a ragged batch of scans; bit-equal to that host chain wherever no projected coordinate sits on
+ * a rounding boundary (a half-integer u or v).  Per job, in file order i = 0..n-1:
+ *   points with !(x >= 0) are dropped; (X, Y, Z) = P . (x, y, z, 1) in float64 (products summed left to right, no fma),
+ *   c = rint(X/Z) - 1, r = rint(Y/Z) - 1, kept iff 0 <= c < w && 0 <= r < h as doubles (NaN and infinities fail);
+ *   depth d = vel_depth ? x : Z, negative -> 0, cast to float32;
+ *   pixel (r, c) takes the d of its kept point with the largest i; then, the reference's rule with its index arithmetic: for
+ *   every g = r*(w-1) + c shared by >= 2 kept points, the pixel of the member with the smallest i receives the smallest d of the
+ *   group ((r, 0) and (r-1, w-1) share a g);
+ *   out[R][C] = map[ys[R]][xs[flip ? gw-1-C : C]], ys / xs = clip(rint((k + 0.5) * n_in / n_out - 0.5), 0, n_in - 1) in float64.
+ * Three launches per MDX_VELO_JOBS jobs (project + clear the touched scratch cells; integer atomicMax / atomicAdd votes; one
+ * thread per output pixel gathers): no float atomics, nothing depends on arrival order, the same bits at every call.  The
+ * workspace needs NO clearing and may hold anything: a cell is believed only if the point it names lies on it.
+ * Jobs are a HOST array (passed to the kernels by value); points / out are DEVICE pointers; no host synchronisation. */
+#define MDX_VELO_JOBS 16
+typedef struct mdx_velodyne_job {
+    const float *points;         /* n rows of `stride` floats (x, y, z[, reflectance: never read]); may be NULL when n == 0 */
+    float *out;                  /* [gh][gw], every element written (0 = no return) */
+    double P[12];                /* 3x4 row-major: P_rect @ R_cam2rect @ velo2cam, formed on the host in float64 */
+    int n, stride;               /* stride: 3 or 4 */
+    int h, w;                    /* native image size, w >= 2 */
+    int gh, gw;                  /* output size */
+    int vel_depth, flip;
+} mdx_velodyne_job;
+/* bytes that `count` jobs of at most nmax points on native grids of at most hmax x wmax need (8 per point, 16 per pixel, each
+ * job's share rounded up to 16); 0 for an argument outside the ranges mdx_velodyne_depth accepts */
+size_t mdx_velodyne_workspace_bytes(int count, int nmax, int hmax, int wmax);
+/* MDX_ERR_NULL_POINTER: jobs, an out, or points with n > 0 is NULL.  MDX_ERR_BAD_SHAPE: count < 0, n < 0, h < 1, w < 2, gh or
+ * gw < 1, h*w or gh*gw beyond int32.  MDX_ERR_UNSUPPORTED: a stride other than 3 or 4.  MDX_ERR_WORKSPACE: workspace NULL or
+ * smaller than the jobs need (the sum of their own shares).  MDX_ERR_MISALIGNED: workspace not 16-byte aligned.  All of them
+ * before anything is launched.  count == 0 launches nothing. */
+int mdx_velodyne_depth(const mdx_velodyne_job *jobs, int count, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ import torch  # noqa: E402
 importlib.import_module("digging-into-self-supervised-monocular-depth-estimation_amd")
 
 
-def measure(samples=24, batch=12, reps=20, height=192, width=640, frames=(0, -1, 1), workers=0):
+def measure(samples=24, batch=12, reps=20, height=192, width=640, frames=(0, -1, 1), workers=0, gpu_velo=False):
     import fake_kitti
     from model_loader import KITTIMonoDataset_v2
     from model_loader.kitti import collate_raw
@@ -127,6 +127,8 @@ def measure(samples=24, batch=12, reps=20, height=192, width=640, frames=(0, -1,
             for mode in ("pillow", "gpu_prep"):
                 ds = KITTIMonoDataset_v2(root, names, True, frames, height, width, "jpg", 4)
                 ds.uint8, ds.gpu_prep = True, mode == "gpu_prep"
+                ds.gpu_velo = bool(gpu_velo) and ds.gpu_prep          # --gpu_velodyne 1: the workers hand the scans over
+                out["gpu_velodyne"] = int(bool(gpu_velo))
                 nb = 8 if mode == "pillow" else 40
                 loader = DataLoader(Repeat(ds, (nb + 2 * workers) * batch), batch, False, num_workers=workers, drop_last=True,
                                     pin_memory=torch.cuda.is_available(), prefetch_factor=2,
@@ -235,6 +237,7 @@ def main():
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--workers", type=int, default=0, help="also time the DataLoader with this many worker processes")
+    ap.add_argument("--gpu_velodyne", type=int, default=0, help="--workers: the gpu_prep loader hands the velodyne scans over (model_option)")
     ap.add_argument("--ranks", type=int, default=0, help="host-feed rehearsal: this many independent DataLoader sets side by side")
     ap.add_argument("--seconds", type=float, default=12.0)
     ap.add_argument("--consume", type=float, default=1780.0, help="rehearsal: samples/s one rank's step consumes (the bar is 1.3 x this)")
@@ -249,7 +252,7 @@ def main():
         print(json.dumps(res))
         sys.stderr.write(res.get("verdict", res.get("error", "")) + "\n")
         return
-    print(json.dumps(measure(a.samples, a.batch, a.reps, a.height, a.width, workers=a.workers)))
+    print(json.dumps(measure(a.samples, a.batch, a.reps, a.height, a.width, workers=a.workers, gpu_velo=a.gpu_velodyne)))
 
 
 if __name__ == "__main__":

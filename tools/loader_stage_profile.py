@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a DataLoader worker's time goes per sample on the gpu_prep (decode-only) path -- no GPU needed:
-    python tools/loader_stage_profile.py
+    python tools/loader_stage_profile.py [--gpu_velodyne]
 Stages: JPEG decode of the 3 frames, velodyne -> sparse ground truth, collate (stacking 12 samples' frames), and what the
 worker -> main-process hand-over adds (num_workers=1 DataLoader against the in-process loop).  One core."""
 import importlib
@@ -29,6 +29,8 @@ def main():
         names = fake_kitti.make(root, n_frames=26)
         ds = KITTIMonoDataset_v2(root, names, True, [0, -1, 1], 192, 640, "jpg", 4)
         ds.uint8, ds.gpu_prep = True, True
+        ds.gpu_velo = "--gpu_velodyne" in sys.argv[1:]       # the velodyne stage hands the scan over instead of projecting it
+        out["gpu_velodyne"] = int(ds.gpu_velo)
         n = 48
 
         def per_sample(fn):
