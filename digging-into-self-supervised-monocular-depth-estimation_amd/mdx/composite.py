@@ -91,3 +91,32 @@ def smooth_loss(disp, color, normalize=True):
     gx = gx * torch.exp(-torch.abs(color[:, :, :, :-1] - color[:, :, :, 1:]).mean(1, True))
     gy = gy * torch.exp(-torch.abs(color[:, :, :-1, :] - color[:, :, 1:, :]).mean(1, True))
     return gx.mean() + gy.mean()
+
+
+def sparse_depth_loss(disps, gt, min_depth, max_depth, lo=None, hi=None, eps=1e-3):
+    """Sparse lidar supervision (csrc/sparse_depth.hip has the definition; mdx.functional.sparse_depth_loss is the GPU form) in any
+    float dtype, mask-free: per scale the Charbonnier penalty sqrt(r^2 + eps^2) - eps of r = log depth - log gt over the valid
+    pixels (lo < gt < hi, strict, the bounds taken as float32 numbers as the C-ABI takes them), divided by max(n, 1).
+    -> dict(loss = tensor [nscales], valid = n).  Invalid pixels are replaced before the logarithms, so neither their values nor a
+    non-finite disparity that only they touch reach the result or a gradient; a scaled disparity that is not a positive finite
+    number under a valid pixel makes that scale's term NaN."""
+    _notice()
+    disps = list(disps)
+    lo = float(torch.tensor(min_depth if lo is None else lo, dtype=torch.float32))
+    hi = float(torch.tensor(max_depth if hi is None else hi, dtype=torch.float32))
+    a, b = 1 / max_depth, 1 / min_depth
+    gh, gw = gt.shape[2:]
+    valid = (gt > lo) & (gt < hi)
+    n = valid.sum()
+    denom = torch.clamp(n, min=1)
+    losses = []
+    for disp in disps:
+        g = gt.to(disp.dtype)
+        u = disp if tuple(disp.shape[2:]) == (gh, gw) else TF.interpolate(disp, [gh, gw], mode="bilinear", align_corners=False)
+        sd = a + (b - a) * u
+        usable = (sd > 0) & torch.isfinite(sd)
+        r = -torch.log(torch.where(valid & usable, sd, torch.ones_like(sd))) - torch.log(torch.where(valid, g, torch.ones_like(g)))
+        r = torch.where(valid & ~usable, torch.full_like(r, float("nan")), r)
+        rho = torch.sqrt(r * r + eps * eps) - eps
+        losses.append(torch.where(valid, rho, torch.zeros_like(rho)).sum() / denom)
+    return dict(loss=torch.stack(losses), valid=n.to(disps[0].dtype))

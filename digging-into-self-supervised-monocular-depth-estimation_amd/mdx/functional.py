@@ -1247,3 +1247,82 @@ def depth_monitor(pred, gt, window, min_depth=1e-3, max_depth=80.0):
     api.mdx_depth_monitor(ptr(pred), B, h, w, ptr(gt), gh, gw, r0, r1, c0, c1, min_depth, max_depth, ptr(out),
                           ptr(ws, torch.uint8), nws, stream())
     return out
+
+
+# ---- sparse lidar supervision (csrc/sparse_depth.hip) -----------------------------------------------------------------
+def _sparse_depth_args(what, disps, gt):
+    """-> (nscales, B, gh, gw, h[], w[]) of a call, or MdxError for lists and shapes the kernels refuse."""
+    n = len(disps)
+    if not 1 <= n <= _lib.MAX_SCALES:
+        raise _lib.MdxError("%s: 1..%d scales supported, got %d" % (what, _lib.MAX_SCALES, n))
+    if gt.dim() != 4 or gt.shape[1] != 1:
+        raise _lib.MdxError("%s: the ground truth is %s, not [B,1,gh,gw]" % (what, tuple(gt.shape)))
+    B, _, gh, gw = gt.shape
+    for k, d in enumerate(disps):
+        if d.dim() != 4 or d.shape[0] != B or d.shape[1] != 1 or d.shape[2] > gh or d.shape[3] > gw or d.numel() == 0:
+            raise _lib.MdxError("%s: the disparity of scale %d is %s under a ground truth of %s: not [B,1,h,w] with h <= gh, w <= gw"
+                                % (what, k, tuple(d.shape), tuple(gt.shape)))
+    hs = (C.c_int32 * n)(*[int(d.shape[2]) for d in disps])
+    ws_ = (C.c_int32 * n)(*[int(d.shape[3]) for d in disps])
+    return n, int(B), int(gh), int(gw), hs, ws_
+
+
+class _SparseDepth(torch.autograd.Function):
+    """The depth term of every scale as ONE autograd node -> out [nscales + 1] = (L_0 .. L_{nscales-1}, n): two launches forward,
+    and a backward of one call (a launch per scale) that reads the upstream gradient where it lies, on the device."""
+
+    @staticmethod
+    def forward(ctx, gt, cfg, *disps):
+        gt = _f32c(gt)
+        disps = [_f32c(d) for d in disps]
+        n, B, gh, gw, hs, ws_ = _sparse_depth_args("sparse_depth_loss", disps, gt)
+        dev = gt.device
+        out = torch.empty(n + 1, device=dev, dtype=torch.float32)
+        nws = api.mdx_sparse_depth_workspace_bytes(n, B, gh, gw)
+        ws = workspace(nws, dev)
+        api.mdx_sparse_depth_fwd(n, B, hs, ws_, _lib.ptr_array(disps), ptr(gt), gh, gw, cfg["min_depth"], cfg["max_depth"],
+                                 cfg["lo"], cfg["hi"], cfg["eps"], ptr(out), ptr(ws, torch.uint8), nws, stream())
+        if any(ctx.needs_input_grad[2:]):
+            ctx.save_for_backward(gt, out, *disps)
+            ctx.cfg = cfg
+            ctx.ws = ws              # the backward checks a workspace and does not touch it: the forward's, not a new allocation
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        gt, out, *disps = ctx.saved_tensors
+        cfg = ctx.cfg
+        n, B, gh, gw, hs, ws_ = _sparse_depth_args("sparse_depth_loss", disps, gt)
+        g = _f32c(g_out)                         # [nscales + 1]: the kernels read the first nscales
+        dd = [torch.empty_like(d) for d in disps]
+        nws, ws = api.mdx_sparse_depth_workspace_bytes(n, B, gh, gw), ctx.ws
+        api.mdx_sparse_depth_bwd(n, B, hs, ws_, _lib.ptr_array(disps), ptr(gt), gh, gw, cfg["min_depth"], cfg["max_depth"],
+                                 cfg["lo"], cfg["hi"], cfg["eps"], ptr(out), ptr(g), _lib.ptr_array(dd), ptr(ws, torch.uint8),
+                                 nws, stream())
+        return (None, None) + tuple(d.to(dt) for d, dt in zip(dd, cfg["dtypes"]))
+
+
+def sparse_depth_loss(disps, gt, min_depth, max_depth, lo=None, hi=None, eps=1e-3):
+    """Sparse lidar supervision of every scale's disparity (csrc/sparse_depth.hip has the definition): per valid pixel of `gt`
+    ([B,1,gh,gw]; valid: lo < gt < hi, strict, the bounds taken as float32; default --min_depth / --max_depth) the Charbonnier
+    penalty sqrt(r^2 + eps^2) - eps of r = log depth - log gt, the depth that of disparity2depth(interpolate(disp_k, gh, gw)),
+    summed in double and divided by max(n, 1), n = the valid pixels of the batch.
+    -> dict(loss = tensor [nscales], differentiable in every disparity; valid = n, a float32 scalar tensor: the kernels hand n from
+    the forward to the backward as a float32, exact up to 2^24 = 16.7 M valid pixels per call and rounded to 24 bits beyond --
+    sparse lidar maps stay far below, a DENSE 375x1242 ground truth reaches it at batch 37; terms and gradients then divide by
+    the rounded n, consistently).
+    No synchronisation, capturable, the same bits at every call; under torch.no_grad() the forward launches alone.  No valid pixel:
+    zeros and zero gradients.  A scaled disparity that is not a positive finite number under a valid pixel: that scale's term is
+    NaN (carried, not clamped)."""
+    disps = list(disps)
+    min_depth, max_depth, eps = float(min_depth), float(max_depth), float(eps)
+    lo = min_depth if lo is None else float(lo)
+    hi = max_depth if hi is None else float(hi)
+    if not (min_depth > 0 and max_depth > min_depth and lo < hi and 0 < eps < float("inf")):
+        raise _lib.MdxError("sparse_depth_loss: min_depth %r, max_depth %r, lo %r, hi %r, eps %r" % (min_depth, max_depth, lo, hi, eps))
+    if any(not torch.is_tensor(d) for d in disps) or not torch.is_tensor(gt):
+        raise _lib.MdxError("sparse_depth_loss: disparities and ground truth must be tensors")
+    cfg = dict(min_depth=min_depth, max_depth=max_depth, lo=lo, hi=hi, eps=eps, dtypes=[d.dtype for d in disps])
+    out = _SparseDepth.apply(gt, cfg, *disps)
+    n = len(disps)
+    return dict(loss=out[:n], valid=out[n].detach())

@@ -55,3 +55,16 @@ class SmoothLoss(nn.Module):
         if not disp.is_cuda:
             return C.smooth_loss(disp, color, normalize=True)
         return F.smooth_loss(disp, color, normalize=True)
+
+
+class SparseDepthLoss(nn.Module):
+    """Sparse lidar supervision of the disparities of every scale (no counterpart in the reference; csrc/sparse_depth.hip has the
+    definition): loss(disps, gt) -> dict(loss = [nscales] tensor, valid = the valid ground-truth pixels of the batch)."""
+
+    def __init__(self, min_depth, max_depth, lo=None, hi=None, eps=1e-3):
+        super().__init__()
+        self.min_depth, self.max_depth, self.lo, self.hi, self.eps = min_depth, max_depth, lo, hi, eps
+
+    def forward(self, disps, gt):
+        fn = F.sparse_depth_loss if gt.is_cuda else C.sparse_depth_loss
+        return fn(disps, gt, self.min_depth, self.max_depth, self.lo, self.hi, self.eps)

@@ -101,6 +101,18 @@ def options(argv=None):
     p.add_argument("--loss_stats_static", type=float, default=0.9,
                    help="--loss_stats: an image counts as static when at least this share of its pixels is auto-masked (a reporting "
                         "threshold, in (0, 1])")
+    p.add_argument("--depth_supervision", type=float, default=0.0,
+                   help="W > 0: semi-supervised training from the sparse lidar ground truth of the batch, (\"depth\", 0): W * the mean "
+                        "over the scales of a Charbonnier penalty (eps 1e-3) on log depth - log ground truth, the depth that of the "
+                        "scale's disparity resampled to the ground truth's size, over the pixels with --min_depth < gt < --max_depth, "
+                        "divided by their number (csrc/sparse_depth.hip, model_loss.SparseDepthLoss; forward and gradient on the "
+                        "device, capturable, bit-reproducible).  It gives a mono-only run a metric scale.  A data-parallel run "
+                        "normalises by each rank's OWN valid count, so the exchanged gradient is the mean of the ranks' terms, not the "
+                        "term of the pooled batch.  Prints one line per epoch.  0: off, no loss module is made and none of its kernels run.  Measured "
+                        "(tools/sparse_depth_cost.py, profiles/r14_sparse_depth_cost.txt, LABNOTES 'Sparse lidar supervision'): "
+                        "batch 12 at 192x640 under 375x1242 ground truth, 4.5 %% valid: forward + backward 265 us in 6 launches against 2016 us "
+                        "in 200 launches for the same term in torch ops; the training loop's step -- the captured step and the five eager launches behind "
+                        "it that keep the epoch's sums -- 14.66 -> 15.01 ms (+2.4 %%)")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

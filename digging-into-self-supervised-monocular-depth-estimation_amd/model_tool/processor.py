@@ -93,6 +93,9 @@ class compute(object):
         # False: the step's small ops as the reference spells them -- the scalar tail of the loss as ~5 torch ops per scale, the
         # pose head's output sliced per frame into param2matrix + K @ T (A/B and parity tests; same numbers)
         self.fused_tail = self.fused and _opt(opt, "fused_tail", True)
+        # --depth_supervision W > 0: the sparse lidar term joins the loss of every path (_depth_term); 0: no loss module is made, none of its kernels run
+        self.depth_supervision = float(_opt(opt, "depth_supervision", 0.0) or 0.0)
+        self._depth_loss = None
 
     # -- networks ---------------------------------------------------------------------------------
     def _autocast(self):
@@ -366,7 +369,25 @@ class compute(object):
             # the smoothness term of every scale with each of its passes launched once (2 launches, not 16)
             s.smooth_multi = len(opt.scales) <= 4 and target.is_cuda
         outputs["loss"] = self.loss_path(target)(s, inputs, outputs, setting)
+        if self.depth_supervision > 0:
+            self._depth_term(s, inputs, outputs)
         return outputs
+
+    def _depth_term(self, s, inputs, outputs):
+        """--depth_supervision W: W * mean_k L_k on top of whichever path formed outputs["loss"], L_k the sparse lidar term of
+        scale k (model_loss.SparseDepthLoss: csrc/sparse_depth.hip for GPU tensors, mdx/composite.py for CPU ones) over the
+        disparities the path itself took; forward only under torch.no_grad().  Nothing here reads the host."""
+        gt = inputs.get(("depth", 0))
+        if not torch.is_tensor(gt):
+            raise ValueError("--depth_supervision %g needs the ground truth (\"depth\", 0) in every batch, and this one has none "
+                           "(a loader built with load_depth off?)" % self.depth_supervision)
+        if self._depth_loss is None:
+            self._depth_loss = SparseDepthLoss(self.opt.min_depth, self.opt.max_depth)
+        gt = gt.float()
+        res = self._depth_loss(s.disps, gt if gt.dim() == 4 else gt.unsqueeze(1))
+        outputs["loss_depth"] = res["loss"].detach()
+        outputs["depth_valid"] = res["valid"]
+        outputs["loss"] = outputs["loss"] + self.depth_supervision * res["loss"].mean()
 
     def _scalar_tail(self, s, setting, mean_min, smooth_all):
         """processor.py:208-217 around a path's mean_min(k, scale).  smooth_all: every scale's smoothness term

@@ -81,8 +81,10 @@ def _plain(v):
 
 def _static_keys(tr):
     """The batch entries a captured step reads, copied into its static buffers (the velodyne ground truth is read by
-    control.metric from the batch itself, never by the step)."""
-    return lambda k: tr.compute._step_reads(k) and not (isinstance(k, tuple) and k[0] == "depth")
+    control.metric from the batch itself and not by the step -- unless --depth_supervision puts it into the loss: then it is a
+    static buffer like the others, copied per replay)."""
+    supervised = float(getattr(tr.opt, "depth_supervision", 0.0) or 0.0) > 0
+    return lambda k: tr.compute._step_reads(k) and (supervised or not (isinstance(k, tuple) and k[0] == "depth"))
 
 
 class graphed_step(object):
@@ -274,6 +276,8 @@ class trainer(object):
         # --loss_stats: the passes issued since the last report (the history is reset with every report), how many of them did not
         # take the kernels, {pass: training step} for them, and the passes of the whole run
         self._loss_stat_passes, self._loss_stat_torch, self._loss_stat_steps, self._loss_stat_total = 0, 0, {}, 0
+        # --depth_supervision: the epoch's sums of the term and of the valid pixels, kept on the device, and the steps behind them
+        self._depth_acc, self._depth_steps = None, 0
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if torch.cuda.is_available():
@@ -517,6 +521,28 @@ class trainer(object):
         self.setting.optim["loss_stats"].reset_history()
         self._loss_stat_passes, self._loss_stat_torch, self._loss_stat_steps = 0, 0, {}
 
+    def depth_supervision_add(self, outputs):
+        """--depth_supervision: the step's mean term and valid count join the epoch's sums where they are, on the device (float64:
+        the sums of the counts stay exact); nothing is read here.  Five small eager launches behind every step, outside the
+        captured graph: part of the option's per-step cost (tools/sparse_depth_cost.py --what step issues them too)."""
+        term, valid = outputs["loss_depth"], outputs["depth_valid"]
+        if self._depth_acc is None:
+            self._depth_acc = torch.zeros(2, dtype=torch.float64, device=term.device)
+        self._depth_acc += torch.stack([term.mean().double(), valid.double()])
+        self._depth_steps += 1
+
+    def depth_supervision_report(self):
+        """-> the line rank 0 prints after an epoch: the mean of the term over the epoch's steps and the mean valid ground-truth
+        pixels per image, of THIS rank's batches.  The one read of the host of --depth_supervision; starts the sums again.  (A
+        step's count is the kernels' float32 n: exact up to 2^24 valid pixels per batch, mdx.functional.sparse_depth_loss.)"""
+        steps = self._depth_steps
+        term, valid = self._depth_acc.tolist() if steps else (0.0, 0.0)
+        if steps:
+            self._depth_acc.zero_()
+        self._depth_steps = 0
+        return ("depth supervision: weight %g, mean term %.6g, %.1f valid pixels per image over %d steps"
+                % (self.compute.depth_supervision, term / max(steps, 1), valid / max(steps * self.opt.batch, 1), steps))
+
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
         (--noise cpu: torch.randn on the CPU + a copy from pageable memory), not with a non-RCCL process group.  With more than
@@ -578,6 +604,7 @@ class trainer(object):
         # --loss_stats N: statistics of the loss path's maps behind every N-th step of the run, reported like --grad_stats; the
         # report covers rank 0's own batches
         loss_every = int(getattr(self.opt, "loss_stats", 0) or 0) if "loss_stats" in self.setting.optim else 0
+        supervised = self.compute.depth_supervision > 0      # --depth_supervision: one line per epoch, read once per epoch
         for epoch in range(start, self.opt.epoch):
             batch_train = {k: [] for k in names}
             batch_valid = {k: [] for k in names}
@@ -595,6 +622,8 @@ class trainer(object):
                     self.grad_stats(done)
                 if loss_every > 0 and done % loss_every == 0:
                     self.loss_stats(train_outputs, done)
+                if supervised:
+                    self.depth_supervision_add(train_outputs)
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
@@ -619,8 +648,11 @@ class trainer(object):
             for key in names:
                 epoch_train[key].append(mean_train[key])
                 epoch_valid[key].append(mean_valid[key])
+            depth_line = self.depth_supervision_report() if supervised else None
             if self.rank == 0:
                 self.control.print(epoch, mean_train, mean_valid)
+                if depth_line:
+                    print(depth_line, flush=True)
                 optimizer = self.setting.optim["optimizer"]
                 if getattr(optimizer, "guarded", False):
                     g = optimizer.guard_stats()

@@ -735,6 +735,37 @@ size_t mdx_velodyne_workspace_bytes(int count, int nmax, int hmax, int wmax);
  * before anything is launched.  count == 0 launches nothing. */
 int mdx_velodyne_depth(const mdx_velodyne_job *jobs, int count, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- sparse lidar supervision: a depth term beside the fused loss (csrc/sparse_depth.hip; mdx.functional.sparse_depth_loss).
+ * disp[k]: float32 contiguous [B,1,h[k],w[k]], k < nscales (1..MDX_MAX_SCALES); gt: float32 contiguous [B,1,gh,gw], 0 = no return;
+ * gh >= h[k] and gw >= w[k].  A ground-truth pixel is VALID when gt > lo && gt < hi (strict: NaN, infinities and the bounds
+ * themselves are invalid); n = the valid pixels of the batch.  Per valid pixel (b,Y,X) and scale:
+ *   u = the bilinear sample of disp[k] at (Y,X) on the gh x gw grid, align_corners=False (the element itself when the sizes are equal),
+ *   sd = a + b*u with a = 1/max_depth, b = 1/min_depth - 1/max_depth as mdx_disparity2depth_fwd forms them,
+ *   r = -log(sd) - log(gt),  rho = sqrt(r^2 + eps^2) - eps.
+ * out[k] = L_k = (sum of rho over the valid pixels, in double, in a fixed order) / max(n, 1); out[nscales] = n (float32: exact up to
+ * 2^24).  n == 0: every L_k is 0.  An sd that is not a positive finite number under a valid pixel makes L_k NaN; a non-finite
+ * disparity that only invalid pixels touch changes nothing.
+ * mdx_sparse_depth_bwd: ddisp[k][b,i,j] = gout[k] / max(n,1) * sum over the valid pixels of (r / sqrt(r^2+eps^2)) * (-b / sd) *
+ * wy(Y,i) * wx(X,j) -- a per-destination sum in a fixed order, every element written (0 where nothing reaches it); `out` is the
+ * forward's (read for n), gout a DEVICE array of nscales floats.
+ * h, w, disp, ddisp are HOST arrays; gt, out, gout, workspace and what disp / ddisp point to are DEVICE memory.  The forward is two
+ * launches, the backward one per scale; no floating-point atomics, nothing to clear between calls, the same inputs give the same
+ * bits at every call; no host synchronisation (capturable).  The workspace (mdx_sparse_depth_workspace_bytes; 0 for sizes the calls
+ * refuse; 8-byte aligned; contents need not survive between the two calls) is asked for and checked by both, but only the forward
+ * uses it: the backward as it is built (a recomputing gather) neither reads nor writes it, so the forward's buffer can be handed
+ * over again; the argument is there for a form that stores per-pixel coefficients first.
+ * Refusals, all before anything is launched, in this order: MDX_ERR_NULL_POINTER (h, w, disp, an entry of it, gt, out; bwd: gout,
+ * ddisp, an entry of it); MDX_ERR_BAD_SHAPE (nscales out of range, a size < 1, gh < h[k] or gw < w[k], B*gh*gw >= 2^32,
+ * min_depth <= 0, max_depth <= min_depth, !(lo < hi), eps not finite or <= 0); MDX_ERR_WORKSPACE (NULL or too small);
+ * MDX_ERR_MISALIGNED (a float pointer not 4-byte, the workspace not 8-byte aligned). */
+size_t mdx_sparse_depth_workspace_bytes(int nscales, int B, int gh, int gw);
+int mdx_sparse_depth_fwd(int nscales, int B, const int *h, const int *w, const float *const *disp, const float *gt, int gh, int gw,
+                         double min_depth, double max_depth, float lo, float hi, double eps, float *out, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int mdx_sparse_depth_bwd(int nscales, int B, const int *h, const int *w, const float *const *disp, const float *gt, int gh, int gw,
+                         double min_depth, double max_depth, float lo, float hi, double eps, const float *out, const float *gout,
+                         float *const *ddisp, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
