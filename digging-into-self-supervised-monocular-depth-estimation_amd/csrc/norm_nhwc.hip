@@ -337,6 +337,216 @@ __global__ __launch_bounds__(NB) void bn_nhwc_bwd_apply_kernel(const T *__restri
     }
 }
 
+// ---- backward with a residual, float32: dz is formed ONCE ------------------------------------------------------------
+// Both passes above form the same dz = (dy [+ dy2]) * (y > 0) from four maps and the apply pass writes it out as d_res: ten
+// map-sized streams.  Here the statistics pass stores dz to d_res (4 reads, 1 write) and the apply pass reads d_res and x only
+// (2 reads, 1 write): eight.  The same float32 expression, stored exactly, so the same bits; not for bfloat16, whose stored
+// d_res is rounded while dx takes the unrounded dz.  Kernels of their own: the instantiations above keep their registers.
+template <typename T>
+__global__ __launch_bounds__(NB) void bn_nhwc_bwd_stats_dz_kernel(const T *__restrict__ dy, const T *__restrict__ dy2,
+                                                                  const T *__restrict__ y, const T *__restrict__ x,
+                                                                  const float *__restrict__ save_mean,
+                                                                  const float *__restrict__ save_invstd, int M, int C, int CVB,
+                                                                  int PL, int RB, int relu, float *__restrict__ part,
+                                                                  T *__restrict__ dres)
+{
+    constexpr int N = VecN<T>::N;
+    __shared__ float lds[2 * NB * N];
+    const Pos p = position<N>(M, C, CVB, PL, RB);
+    float a[N], q[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) a[j] = q[j] = 0.f;
+    if (p.active) {
+        float mean[N], invstd[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            mean[j] = save_mean[(size_t)p.g * C + p.cv * N + j];
+            invstd[j] = save_invstd[(size_t)p.g * C + p.cv * N + j];
+        }
+        const size_t base = (size_t)p.g * M * C + (size_t)p.cv * N;
+        const T *pd = dy + base, *pd2 = dy2 ? dy2 + base : nullptr, *py = y + base, *px = x + base;
+        T *orr = dres + base;
+        auto acc = [&](const Vec<T, N> &vd, const Vec<T, N> &vd2, const Vec<T, N> &vy, const Vec<T, N> &vx, size_t off) {
+            Vec<T, N> wr;
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                float d = to_float(vd.v[j]);
+                if (pd2) d += to_float(vd2.v[j]);
+                const float dz = (relu && !(to_float(vy.v[j]) > 0.f)) ? 0.f : d;
+                a[j] += dz;
+                q[j] = __builtin_fmaf(dz, (to_float(vx.v[j]) - mean[j]) * invstd[j], q[j]);
+                wr.v[j] = from_float<T>(dz);
+            }
+            store_vec<T, N>(orr + off, wr);
+        };
+        int r = p.r0 + p.pl;
+        constexpr int U = 2;          // rows in flight, as in bn_nhwc_bwd_stats_kernel (4: no faster, the pass streams at HBM rate)
+        for (; r + (U - 1) * PL < p.r1; r += U * PL) {
+            Vec<T, N> d[U], e[U], yy[U], xx[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t o = (size_t)(r + u * PL) * C;
+                d[u] = load_vec<T, N>(pd + o);
+                yy[u] = load_vec<T, N>(py + o);
+                xx[u] = load_vec<T, N>(px + o);
+                e[u] = Vec<T, N>{};
+                if (pd2) e[u] = load_vec<T, N>(pd2 + o);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc(d[u], e[u], yy[u], xx[u], (size_t)(r + u * PL) * C);
+        }
+        for (; r < p.r1; r += PL) {
+            const size_t o = (size_t)r * C;
+            Vec<T, N> e = {};
+            if (pd2) e = load_vec<T, N>(pd2 + o);
+            acc(load_vec<T, N>(pd + o), e, load_vec<T, N>(py + o), load_vec<T, N>(px + o), o);
+        }
+    }
+    block_partials<N>(a, q, lds, CVB, PL, C, part + ((size_t)p.g * gridDim.x + blockIdx.x) * 2 * C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(NB) void bn_nhwc_bwd_apply_dz_kernel(const T *__restrict__ dz_map, const T *__restrict__ x,
+                                                                  const float *__restrict__ gamma,
+                                                                  const float *__restrict__ save_mean,
+                                                                  const float *__restrict__ save_invstd,
+                                                                  const float *__restrict__ totals, int M, int C, int CVB, int PL,
+                                                                  int RB, T *__restrict__ dx)
+{
+    constexpr int N = VecN<T>::N;
+    const Pos p = position<N>(M, C, CVB, PL, RB);
+    if (!p.active) return;
+    float mean[N], invstd[N], k0[N], mdz[N], mdzx[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const int c = p.cv * N + j;
+        mean[j] = save_mean[(size_t)p.g * C + c];
+        invstd[j] = save_invstd[(size_t)p.g * C + c];
+        k0[j] = gamma[c] * invstd[j];
+        mdz[j] = totals[((size_t)p.g * 2 + 0) * C + c];
+        mdzx[j] = totals[((size_t)p.g * 2 + 1) * C + c];
+    }
+    const size_t base = (size_t)p.g * M * C + (size_t)p.cv * N;
+    const T *pz = dz_map + base, *px = x + base;
+    T *ox = dx + base;
+    auto apply = [&](const Vec<T, N> &vz, const Vec<T, N> &vx, size_t off) {
+        Vec<T, N> wx;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const float dz = to_float(vz.v[j]);
+            const float xh = (to_float(vx.v[j]) - mean[j]) * invstd[j];
+            wx.v[j] = from_float<T>(k0[j] * (dz - mdz[j] - xh * mdzx[j]));
+        }
+        store_vec<T, N>(ox + off, wx);
+    };
+    int r = p.r0 + p.pl;
+    for (; r + 3 * PL < p.r1; r += 4 * PL) {
+        const size_t o0 = (size_t)r * C, o1 = (size_t)(r + PL) * C, o2 = (size_t)(r + 2 * PL) * C, o3 = (size_t)(r + 3 * PL) * C;
+        const Vec<T, N> z0 = load_vec<T, N>(pz + o0), z1 = load_vec<T, N>(pz + o1), z2 = load_vec<T, N>(pz + o2), z3 = load_vec<T, N>(pz + o3);
+        const Vec<T, N> x0 = load_vec<T, N>(px + o0), x1 = load_vec<T, N>(px + o1), x2 = load_vec<T, N>(px + o2), x3 = load_vec<T, N>(px + o3);
+        apply(z0, x0, o0); apply(z1, x1, o1); apply(z2, x2, o2); apply(z3, x3, o3);
+    }
+    for (; r < p.r1; r += PL) {
+        const size_t o = (size_t)r * C;
+        apply(load_vec<T, N>(pz + o), load_vec<T, N>(px + o), o);
+    }
+}
+
+// ---- the ResNet stem, forward: relu(bn(x)) followed by max-pool 3x3 / 2 / 1 in ONE apply pass -----------------------------
+// Window and tap logic: glue_nhwc.hip's maxpool3s2_nhwc_fwd_kernel.  A thread walks every PL-th row (pooled pixel) of its block as
+// above; the pixel a row is (image, y, x) is carried along, one add and two compares per step instead of two divisions per row.
+struct Pix { int b, y, x; };
+__host__ __device__ __forceinline__ Pix pix_of(int r, int H, int W)     // (on the host: the step PL as images, rows, columns)
+{
+    Pix p;
+    p.b = r / (H * W);
+    const int rem = r - p.b * H * W;
+    p.y = rem / W;
+    p.x = rem - p.y * W;
+    return p;
+}
+__device__ __forceinline__ void pix_step(Pix &p, const Pix &s, int H, int W)     // every part of s is below its modulus: one carry each
+{
+    p.x += s.x;
+    p.y += s.y;
+    p.b += s.b;
+    if (p.x >= W) { p.x -= W; ++p.y; }
+    if (p.y >= H) { p.y -= H; ++p.b; }
+}
+
+// forward, pass 2: a thread owns pooled pixels.  It normalises the nine x taps of a window with the apply pass's own expressions,
+// takes the maximum by the pool's rule (first in-bounds tap, strict >, NaN propagates) and, when the map itself is wanted
+// (y != nullptr: the depth encoder's skip connection), writes the up to four y pixels (2yo..2yo+1, 2xo..2xo+1) of its window
+// -- every y pixel exactly once.  B: images per group; rows = the Mo = B * Ho * Wo pooled pixels of a group.
+template <typename T>
+__global__ __launch_bounds__(NB) void bn_pool_nhwc_fwd_apply_kernel(const T *__restrict__ x, const float *__restrict__ gamma,
+                                                                    const float *__restrict__ beta,
+                                                                    const float *__restrict__ save_mean,
+                                                                    const float *__restrict__ save_invstd, int B, int Mo, int C, int H,
+                                                                    int W, int Ho, int Wo, int CVB, int PL, int RB, Pix step,
+                                                                    T *__restrict__ y, T *__restrict__ pooled,
+                                                                    uint8_t *__restrict__ arg)
+{
+    constexpr int N = VecN<T>::N;
+    const Pos p = position<N>(Mo, C, CVB, PL, RB);
+    if (!p.active) return;
+    float scale[N], shift[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const int c = p.cv * N + j;
+        scale[j] = gamma[c] * save_invstd[(size_t)p.g * C + c];
+        shift[j] = beta[c] - save_mean[(size_t)p.g * C + c] * scale[j];
+    }
+    const size_t c0 = (size_t)p.cv * N;
+    int r = p.r0 + p.pl;
+    Pix po = pix_of(r, Ho, Wo);
+    for (; r < p.r1; r += PL, pix_step(po, step, Ho, Wo)) {
+        const size_t img = ((size_t)p.g * B + po.b) * H * W * C + c0;
+        Vec<T, N> tap[9];
+        bool ok[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = 2 * po.y - 1 + k / 3, xx = 2 * po.x - 1 + k % 3;
+            ok[k] = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            tap[k] = load_vec<T, N>(x + img + ((size_t)(ok[k] ? yy : 0) * W + (ok[k] ? xx : 0)) * C);
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const float f = __builtin_fmaf(to_float(tap[k].v[j]), scale[j], shift[j]);
+                tap[k].v[j] = from_float<T>(f < 0.f ? 0.f : f);
+            }
+        Vec<T, N> o;
+        Vec<uint8_t, N> a;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            float best = -INFINITY;
+            int bi = -1;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                if (!ok[k]) continue;
+                const float v = to_float(tap[k].v[j]);
+                if (bi < 0) bi = k;
+                if (v > best || v != v) { best = v; bi = k; }
+            }
+            o.v[j] = from_float<T>(best);
+            a.v[j] = (uint8_t)bi;
+        }
+        const size_t off = ((size_t)p.g * Mo + r) * C + c0;
+        store_vec<T, N>(pooled + off, o);
+        store_vec<uint8_t, N>(arg + off, a);
+        if (y) {
+#pragma unroll
+            for (int k = 4; k < 9; ++k) {
+                if (k == 6 || !ok[k]) continue;               // taps 4, 5, 7, 8 = pixels (2yo, 2xo), (2yo, 2xo+1), (2yo+1, 2xo), (2yo+1, 2xo+1)
+                const int yy = 2 * po.y - 1 + k / 3, xx = 2 * po.x - 1 + k % 3;
+                store_vec<T, N>(y + img + ((size_t)yy * W + xx) * C, tap[k]);
+            }
+        }
+    }
+}
+
 }  // namespace nhwc
 }  // namespace mdx
 
@@ -389,7 +599,18 @@ MDX_EXPORT int mdx_bn_act_nhwc_fwd(const void *x, const void *res, const float *
     return check_launch();
 }
 
-// dy2 (optional): a second upstream gradient of y, added on the way in.  dres (optional): gradient of the residual input.
+// A/B switch of the float32 residual backward (1, the default: dz formed once, see bn_nhwc_bwd_stats_dz_kernel; 0: both passes
+// form it, as for bfloat16).  Same bits either way.  Returns the previous setting; not for concurrent use with a launch.
+static int g_dz_once = 1;
+MDX_EXPORT int mdx_bn_dz_once(int on)
+{
+    const int was = g_dz_once;
+    g_dz_once = on != 0;
+    return was;
+}
+
+// dy2 (optional): a second upstream gradient of y, added on the way in.  dres (optional): gradient of the residual input, on
+// storage of its own.
 // y NULL (relu, no residual, beta given): the ReLU mask is re-derived from x with the forward pass's own expressions instead of
 // being read -- one map less in each of the two passes.
 MDX_EXPORT int mdx_bn_act_nhwc_bwd(const void *dy, const void *dy2, const void *y, const void *x, const float *gamma,
@@ -413,6 +634,16 @@ MDX_EXPORT int mdx_bn_act_nhwc_bwd(const void *dy, const void *dy2, const void *
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid_s(gs.nblk, gs.t.ny, groups), grid_a(ga.nblk, ga.t.ny, groups), block(NB);
     const bool maskx = !y;              // (checked above: only with relu, beta and no residual)
+    if (dres && dtype == MDX_F32 && g_dz_once) {       // dz formed once: stored to dres by the statistics pass, read back by the apply pass
+        using T = float;
+        hipLaunchKernelGGL((bn_nhwc_bwd_stats_dz_kernel<T>), grid_s, block, 0, st, (const T *)dy, (const T *)dy2, (const T *)y, (const T *)x,
+                           save_mean, save_invstd, M, C, gs.t.CVB, gs.t.PL, gs.RB, relu, part, (T *)dres);
+        hipLaunchKernelGGL(bn_nhwc_bwd_finalize_kernel, dim3((C + FC - 1) / FC), dim3(FC * FS), 0, st, part, gs.nblk, C, groups, (double)M,
+                           totals, dgamma, dbeta);
+        hipLaunchKernelGGL((bn_nhwc_bwd_apply_dz_kernel<T>), grid_a, block, 0, st, (const T *)dres, (const T *)x, gamma, save_mean,
+                           save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, (T *)dx);
+        return check_launch();
+    }
     dispatch_dtype_flag(dtype, maskx, [&](auto t, auto mx) {
         using T = typename decltype(t)::type;
         hipLaunchKernelGGL((bn_nhwc_bwd_stats_kernel<T, decltype(mx)::value>), grid_s, block, 0, st, (const T *)dy, (const T *)dy2,
@@ -426,5 +657,42 @@ MDX_EXPORT int mdx_bn_act_nhwc_bwd(const void *dy, const void *dy2, const void *
                            (const T *)y, (const T *)x, gamma, beta, save_mean, save_invstd, totals, M, C, ga.t.CVB, ga.t.PL, ga.RB, relu,
                            (T *)dx, (T *)dres);
     });
+    return check_launch();
+}
+
+// ---- the stem, forward: relu(bn(x)) -> max-pool 3x3 / 2 / 1 as one operator (float32) ------------------------------------------
+static int bn_pool_args_ok(int B, int C, int H, int W, int groups, int dtype)
+{
+    const int bad = nhwc_args_ok(B, C, H, W, groups, dtype);
+    if (bad) return bad;
+    return dtype == MDX_F32 ? MDX_OK : MDX_ERR_BAD_SHAPE;          // bfloat16 maps take mdx_bn_act_nhwc_* + mdx_maxpool3s2_nhwc_*
+}
+
+// x [groups*B][H][W][C] -> pooled, arg [groups*B][Ho][Wo][C] and, when y is not NULL, y [groups*B][H][W][C]: statistics and
+// finalize are mdx_bn_act_nhwc_fwd's; the apply pass normalises the nine taps of every window and never reads a stored y.  The
+// backward stays mdx_maxpool3s2_nhwc_bwd + mdx_bn_act_nhwc_bwd (y NULL): a gather of the pooled gradient inside both of its passes
+// was measured and did not pay (LABNOTES).
+MDX_EXPORT int mdx_bn_pool_nhwc_fwd(const void *x, const float *gamma, const float *beta, float *run_mean, float *run_var, void *y,
+                                    void *pooled, uint8_t *arg, float *save_mean, float *save_invstd, int B, int C, int H, int W,
+                                    int groups, float eps, float momentum, int dtype, void *workspace, size_t workspace_bytes,
+                                    void *stream)
+{
+    if (!x || !gamma || !beta || !pooled || !arg || !save_mean || !save_invstd || !workspace) return MDX_ERR_NULL_POINTER;
+    if ((run_mean == nullptr) != (run_var == nullptr)) return MDX_ERR_NULL_POINTER;
+    const int bad = bn_pool_args_ok(B, C, H, W, groups, dtype);
+    if (bad) return bad;
+    if (!aligned(x, 16) || !aligned(pooled, 16) || !aligned(arg, 8) || (y && !aligned(y, 16))) return MDX_ERR_MISALIGNED;
+    if (workspace_bytes < mdx_bn_nhwc_workspace_bytes(B, C, H, W, groups, dtype)) return MDX_ERR_WORKSPACE;
+    using T = float;
+    const int M = B * H * W, N = vec_elems(dtype), Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Mo = B * Ho * Wo;
+    const Rows gs = make_rows(M, C, N, STATS_FWD_BLOCKS, STATS_ITERS), ga = make_rows(Mo, C, N, APPLY_MAX_BLOCKS, APPLY_ITERS);
+    float *part = (float *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid_s(gs.nblk, gs.t.ny, groups), grid_a(ga.nblk, ga.t.ny, groups), block(NB);
+    hipLaunchKernelGGL((bn_nhwc_fwd_stats_kernel<T>), grid_s, block, 0, st, (const T *)x, M, C, gs.t.CVB, gs.t.PL, gs.RB, part);
+    hipLaunchKernelGGL(bn_nhwc_fwd_finalize_kernel, dim3((C + FC - 1) / FC), dim3(FC * FS), 0, st, part, gs.nblk, C, groups, (double)M,
+                       eps, momentum, save_mean, save_invstd, run_mean, run_var);
+    hipLaunchKernelGGL((bn_pool_nhwc_fwd_apply_kernel<T>), grid_a, block, 0, st, (const T *)x, gamma, beta, save_mean, save_invstd, B, Mo,
+                       C, H, W, Ho, Wo, ga.t.CVB, ga.t.PL, ga.RB, pix_of(ga.t.PL, Ho, Wo), (T *)y, (T *)pooled, arg);
     return check_launch();
 }

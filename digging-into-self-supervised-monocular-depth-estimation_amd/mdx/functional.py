@@ -9,6 +9,7 @@ Fine-grained ops mirror model_layer/warp.py and model_loss/model_loss.py one to 
 All tensors must be CUDA/HIP float32; there is no CPU path.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -1115,6 +1116,8 @@ class _BnAct(torch.autograd.Function):
         nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, code) if cl else api.mdx_bn_workspace_bytes(Bg, Cc, H, W)
         ws = workspace(nws, x.device)
         if cl:
+            if has_res:
+                _dz_once_from_env()
             api.mdx_bn_act_nhwc_bwd(
                 ptr(dy, x.dtype, cl=True), ptr(dy2, x.dtype, optional=True, cl=True), ptr(y, x.dtype, optional=True, cl=True),
                 ptr(x, x.dtype, cl=True), ptr(weight), ptr(bias, optional=True), ptr(save_mean), ptr(save_invstd),
@@ -1139,6 +1142,96 @@ def bn_act(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1, r
     gradients separately and adds them inside its kernel instead of autograd doing so in a pass of its own."""
     return _BnAct.apply(x, residual, weight, bias, running_mean, running_var, float(eps), float(momentum), bool(relu),
                         int(groups), bool(fork))
+
+
+# A/B switch of csrc/norm_nhwc.hip's float32 residual backward (dz formed once): MDX_BN_DZ_ONCE=0 takes the form that forms it in
+# both passes.  Same bits either way; read when the first backward with a residual runs.
+_dz_once_set = False
+
+
+def bn_dz_once(on):
+    """Set the switch (process-wide); returns the previous setting."""
+    global _dz_once_set
+    _dz_once_set = True
+    return bool(api.mdx_bn_dz_once(int(bool(on))))
+
+
+def _dz_once_from_env():
+    if not _dz_once_set:
+        bn_dz_once(os.environ.get("MDX_BN_DZ_ONCE", "1") != "0")
+
+
+def bn_act_pool_ok(x):
+    """The map the fused stem (csrc/norm_nhwc.hip: mdx_bn_pool_nhwc_fwd) takes: channels-last float32 on the GPU, whole channel vectors."""
+    return _cl_map(x, (torch.float32,)) and _nhwc_ok(x.dtype, x.shape[1])
+
+
+class _BnActPool(torch.autograd.Function):
+    """relu(bn(x)) -> MaxPool2d(3, 2, 1) of the ResNet stem as one node: _BnAct(fork=True) -> _MaxPool3s2(fork=True) bit for bit.
+    Forward: one apply pass writes the pooled map (and the ReLU map only when someone reads it); no pass re-reads the ReLU map.
+    Backward: the two nodes' own kernels (a gather of the pooled gradient inside the batch-norm passes did not pay, LABNOTES)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, groups, need_map):
+        B, Cc, H, W = x.shape
+        if not bn_act_pool_ok(x):
+            raise _lib.MdxError("bn_act_pool takes a channels-last float32 GPU map with C %% 4 == 0, got %s %s on %s"
+                                % (tuple(x.shape), x.dtype, x.device))
+        if B % groups:
+            raise _lib.MdxError("bn_act_pool: batch %d is not divisible into %d groups" % (B, groups))
+        weight, bias = _f32c(weight), _f32c(bias)
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty_like(x) if need_map else None
+        pooled = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=x.dtype, memory_format=_CL)
+        arg = torch.empty(B, Cc, Ho, Wo, device=x.device, dtype=torch.uint8, memory_format=_CL)
+        save_mean = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
+        save_invstd = torch.empty(groups, Cc, device=x.device, dtype=torch.float32)
+        Bg = B // groups
+        nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, 0)
+        ws = workspace(nws, x.device)
+        api.mdx_bn_pool_nhwc_fwd(ptr(x, x.dtype, cl=True), ptr(weight), ptr(bias), ptr(running_mean, optional=True),
+                                 ptr(running_var, optional=True), ptr(y, x.dtype, optional=True, cl=True),
+                                 ptr(pooled, x.dtype, cl=True), ptr(arg, torch.uint8, cl=True), ptr(save_mean), ptr(save_invstd),
+                                 Bg, Cc, H, W, groups, eps, momentum, 0, ptr(ws, torch.uint8), nws, stream())
+        ctx.save_for_backward(x, bias, weight, save_mean, save_invstd, arg)
+        ctx.groups = groups
+        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var) if t is not None])
+        ctx.set_materialize_grads(False)
+        return y, pooled, pooled.view_as(pooled)
+
+    @staticmethod
+    def backward(ctx, dy, gpool, gpool2):
+        x, bias, weight, save_mean, save_invstd, arg = ctx.saved_tensors
+        groups = ctx.groups
+        dy, _ = _two_grads(dy, None, x.dtype, True, fused_add=True)
+        gpool, gpool2 = _two_grads(gpool, gpool2, x.dtype, True, fused_add=True)
+        if dy is None and gpool is None:
+            return (None,) * 9
+        B, Cc, H, W = x.shape
+        Bg = B // groups
+        gin = None
+        if gpool is not None:        # the pool's gather, then the batch norm with the mask re-derived from x: _MaxPool3s2 / _BnAct's calls
+            gin = torch.empty_like(x)
+            api.mdx_maxpool3s2_nhwc_bwd(ptr(gpool, x.dtype, cl=True), ptr(gpool2, x.dtype, optional=True, cl=True),
+                                        ptr(arg, torch.uint8, cl=True), ptr(gin, x.dtype, cl=True), B, Cc, H, W, 0, stream())
+        dy, dy2 = _two_grads(dy, gin, x.dtype, True, fused_add=True)
+        dx = torch.empty_like(x)
+        dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
+        dbeta = torch.empty(Cc, device=x.device, dtype=torch.float32)
+        nws = api.mdx_bn_nhwc_workspace_bytes(Bg, Cc, H, W, groups, 0)
+        ws = workspace(nws, x.device)
+        api.mdx_bn_act_nhwc_bwd(ptr(dy, x.dtype, cl=True), ptr(dy2, x.dtype, optional=True, cl=True), None, ptr(x, x.dtype, cl=True),
+                                ptr(weight), ptr(bias), ptr(save_mean), ptr(save_invstd), ptr(dx, x.dtype, cl=True), None,
+                                ptr(dgamma), ptr(dbeta), Bg, Cc, H, W, groups, 1, 0, ptr(ws, torch.uint8), nws, stream())
+        return (dx, dgamma, dbeta) + (None,) * 6
+
+
+def bn_act_pool(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1, groups=1, need_map=True):
+    """The ResNet stem after its convolution: y = relu(batch_norm(x)) in training mode (as bn_act), pooled = MaxPool2d(3, 2, 1)(y),
+    for a channels-last float32 map (bn_act_pool_ok) -> (y, pooled, pooled again): what bn_act(fork=True) followed by
+    maxpool3s2(fork=True) return, bit for bit, forward and backward.  need_map=False: y is neither written nor returned (None)
+    -- for an encoder whose stem map nothing reads."""
+    return _BnActPool.apply(x, weight, bias, running_mean, running_var, float(eps), float(momentum), int(groups), bool(need_map))
 
 
 # ---- eval-mode BatchNorm2d fused with residual add and ReLU (csrc/norm_infer.hip) -------------------------------------

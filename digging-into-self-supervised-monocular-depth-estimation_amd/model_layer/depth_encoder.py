@@ -83,13 +83,7 @@ class BatchNorm2d(nn.BatchNorm2d):
                                   residual=residual, relu=relu, fork=fork)
         # csrc/norm.hip: one launch each way for maps up to 24 K elements per channel (kept in registers between the
         # reduction and the apply step), two (statistics pass, apply pass) above -- tools/normbench.py
-        fused = (self.training and x.is_cuda and self.track_running_stats and self.momentum is not None
-                 and self.affine and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 4
-                 and torch.is_grad_enabled() and x.shape[0] % self._batch_groups == 0
-                 and x.shape[0] * x.shape[2] * x.shape[3] >= self.fused_min_elements
-                 # csrc/norm.hip puts (images of a group) x (8 K-element spans of a plane) on a 16-bit grid axis
-                 and (x.shape[0] // self._batch_groups) * ((x.shape[2] * x.shape[3] + 8191) // 8192) <= 65535)
-        if not fused:
+        if not self._train_fused(x):
             out = self(x)
             if residual is not None:
                 out = out + residual
@@ -101,6 +95,34 @@ class BatchNorm2d(nn.BatchNorm2d):
             residual = residual.to(x.dtype)
         return F.bn_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
                         residual=residual, relu=relu, groups=self._batch_groups, fork=fork)
+
+    def _train_fused(self, x):
+        """Training mode on the GPU, a gradient wanted: the fused training kernels serve act() and act_pool()."""
+        return (self.training and x.is_cuda and self.track_running_stats and self.momentum is not None
+                and self.affine and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 4
+                and torch.is_grad_enabled() and x.shape[0] % self._batch_groups == 0
+                and x.shape[0] * x.shape[2] * x.shape[3] >= self.fused_min_elements
+                # csrc/norm.hip puts (images of a group) x (8 K-element spans of a plane) on a 16-bit grid axis
+                and (x.shape[0] // self._batch_groups) * ((x.shape[2] * x.shape[3] + 8191) // 8192) <= 65535)
+
+    def act_pool(self, x, need_map=True, fork=False, fused=True, pool=None):
+        """The ResNet stem: (y, pooled) with y = relu(self(x)), pooled = MaxPool2d(3, 2, 1)(y); fork: pooled as a pair, one tensor
+        per consumer.  A channels-last float32 map that act() would hand to the fused training kernels goes through ONE operator
+        (mdx.functional.bn_act_pool: no pass re-reads y, the backward stores no full-resolution pool gradient, and with
+        need_map=False y is not even written: it comes back as None).  Every other map takes act() and then the pool --
+        mdx.functional.maxpool3s2, or the module `pool` where its kernels do not apply -- and y is returned either way."""
+        from mdx import functional as F
+        if (fused and self._train_fused(x) and F.bn_act_pool_ok(x)
+                and x.shape[0] * x.shape[1] <= 65535):               # the guard of the pool it replaces
+            self._pending_batches += self._batch_groups
+            y, p1, p2 = F.bn_act_pool(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
+                                      groups=self._batch_groups, need_map=need_map)
+            return y, ((p1, p2) if fork else p1)
+        y, y_b = _pair(self.act(x, fork=fork))
+        if (y.is_cuda and y.dtype in (torch.float32, torch.bfloat16)
+                and y.shape[0] * y.shape[1] <= 65535):               # csrc/glue.hip: B*C on a 16-bit grid axis
+            return y, F.maxpool3s2(y_b, fork=fork)     # gather-based backward instead of ATen's atomics (csrc/glue.hip)
+        return y, (pool(y_b) if pool is not None else TF.max_pool2d(y_b, 3, 2, 1))
 
     def _eval_fused(self, x, residual):
         """Eval mode on the GPU with nothing to differentiate: the fused eval kernel serves act()."""
@@ -237,8 +259,9 @@ def resnet_multiimage_input(num_layers, pretrained=True, num_input_images=1):
 class ResnetEncoder(nn.Module):
     """reference: model_layer/depth_encoder.py:65-101.  Returns the five feature maps."""
 
-    def __init__(self, num_layers, pretrained, num_input_images=1):
+    def __init__(self, num_layers, pretrained, num_input_images=1, stem_feature=True):
         super().__init__()
+        self.stem_feature = bool(stem_feature)        # False: nothing reads features[0] (the pose encoder): it is None
         self.num_ch_enc = np.array([64, 64, 128, 256, 512])
         if num_layers not in _CFG:
             raise ValueError("{} is not a valid number of resnet layers".format(num_layers))
@@ -252,6 +275,7 @@ class ResnetEncoder(nn.Module):
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
 
+    fused_stem = True        # False: the stem's batch norm and max-pool as two operators (A/B, parity tests)
     fused_input = True       # False: (x - 0.45) / 0.225 as torch ops on the concatenated frames (A/B, parity tests)
 
     def _normalised_input(self, input_image):
@@ -278,14 +302,9 @@ class ResnetEncoder(nn.Module):
         x = self._normalised_input(input_image)
         # every map below has two consumers (the next layer's first convolution + its identity path, or the decoder's
         # skip connection + the next layer): producers hand their output on as a pair, see BatchNorm2d.act(fork=True)
-        stem, stem_b = _pair(self.encoder.bn1.act(self.encoder.conv1(x), fork=BasicBlock.fork_output))
-        self.features.append(stem)
-        if (stem.is_cuda and stem.dtype in (torch.float32, torch.bfloat16)
-                and stem.shape[0] * stem.shape[1] <= 65535):         # csrc/glue.hip: B*C on a 16-bit grid axis
-            from mdx import functional as F      # gather-based backward instead of ATen's atomics (csrc/glue.hip)
-            x = F.maxpool3s2(stem_b, fork=BasicBlock.fork_output)
-        else:
-            x = self.encoder.maxpool(stem_b)
+        stem, x = self.encoder.bn1.act_pool(self.encoder.conv1(x), need_map=self.stem_feature, fork=BasicBlock.fork_output,
+                                            fused=self.fused_stem, pool=self.encoder.maxpool)
+        self.features.append(stem if self.stem_feature else None)
         for layer in (self.encoder.layer1, self.encoder.layer2, self.encoder.layer3, self.encoder.layer4):
             # a stage's layout is its weights' layout (mdx.layout): a transposing copy only where two stages differ
             x = _pair(layer(to_layout(x, weight_layout(layer)) if x[0].is_cuda else x))

@@ -108,7 +108,8 @@ class setting(object):
         elif opt.pose_type == "shared":
             self.model["pose_decoder"] = PoseDecoder(self.model["encoder"].num_ch_enc, self.num_pose_frames)
         elif opt.pose_type == "separate":
-            self.model["pose_encoder"] = ResnetEncoder(opt.num_layers, opt.weight_init, self.num_pose_frames)
+            # the pose decoder reads features[-1] only: the stem's ReLU map is never written (features[0] is None)
+            self.model["pose_encoder"] = ResnetEncoder(opt.num_layers, opt.weight_init, self.num_pose_frames, stem_feature=False)
             self.model["pose_decoder"] = PoseDecoder(self.model["pose_encoder"].num_ch_enc, num_input_features=1,
                                                      num_frames_to_predict_for=2)
         self.inv_projection = {0: Depth2PointCloud(opt.batch, opt.height, opt.width).to(self.device)}

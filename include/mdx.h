@@ -571,7 +571,22 @@ int mdx_bn_act_nhwc_bwd(const void *dy, const void *dy2, const void *y, const vo
                         const float *beta, const float *save_mean, const float *save_invstd, void *dx, void *dres, float *dgamma,
                         float *dbeta, int B, int C, int H, int W, int groups, int relu, int dtype, void *workspace,
                         size_t workspace_bytes, void *stream);
-/* Between the pose decoder's convolutions   model_layer/pose_decoder.py:24-53 (the convolution runs without its bias).
+/* mdx_bn_act_nhwc_bwd with dres on a float32 map forms dz = (dy [+ dy2]) * (y > 0) once: the statistics pass stores it to dres,
+ * the apply pass reads dres and x only (eight map-sized streams, not ten; the same bits).  dres shares storage with no input.
+ * mdx_bn_dz_once(0) switches this off process-wide (both passes form dz, as for bfloat16), for A/B runs and
+ * tests; it returns the previous setting and must not race a launch. */
+int mdx_bn_dz_once(int on);
+/* The ResNet stem forward, relu(bn(x)) followed by MaxPool2d(3, 2, 1), as one operator (float32 only: dtype 1 is MDX_ERR_BAD_SHAPE
+ * and the caller takes mdx_bn_act_nhwc_fwd + mdx_maxpool3s2_nhwc_fwd, whose results this equals bit for bit).  x, y
+ * [groups*B][H][W][C]; pooled, arg [groups*B][Ho][Wo][C], Ho = (H - 1) / 2 + 1.  Workspace: mdx_bn_nhwc_workspace_bytes.  Three
+ * launches: the statistics and finalize passes of mdx_bn_act_nhwc_fwd, then one pass that normalises the nine x taps of every
+ * window, writes pooled and arg (first maximum wins, NaN propagates) and -- only when y is not NULL -- the map y itself, every pixel
+ * once.  save_mean, save_invstd and arg are what mdx_bn_act_nhwc_bwd (y NULL) and mdx_maxpool3s2_nhwc_bwd take in the backward. */
+int mdx_bn_pool_nhwc_fwd(const void *x, const float *gamma, const float *beta, float *run_mean, float *run_var, void *y,
+                         void *pooled, uint8_t *arg, float *save_mean, float *save_invstd, int B, int C, int H, int W,
+                         int groups, float eps, float momentum, int dtype, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* Between the pose decoder's convolutions  model_layer/pose_decoder.py:24-53 (the convolution runs without its bias).
  * bias_act: y = act(x + bias), x, y [B][H][W][C] channels-last (dtype 0 float32 / 1 bfloat16, C a multiple of the 16-byte vector),
  * bias [C] float32, relu 0 / 1.  bwd: dy, y -> dx, dbias [C]: one launch + a finishing pass over the block partials (workspace).
  * mean_bias: out [B][C] float32 = scale * (mean over H*W of x + bias) -- the head's spatial mean and 0.01 (pose_decoder.py:51-53);
