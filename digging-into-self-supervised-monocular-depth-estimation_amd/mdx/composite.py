@@ -120,3 +120,87 @@ def sparse_depth_loss(disps, gt, min_depth, max_depth, lo=None, hi=None, eps=1e-
         rho = torch.sqrt(r * r + eps * eps) - eps
         losses.append(torch.where(valid, rho, torch.zeros_like(rho)).sum() / denom)
     return dict(loss=torch.stack(losses), valid=n.to(disps[0].dtype))
+
+
+def _sgm_path(C, dy, dx, p1, p2):
+    """One path recursion of stereo_hints over a cost volume C [H,W,D] (int32): rows (dy != 0) or columns (dy == 0) in path order,
+    the predecessors of a whole row / column advanced at once."""
+    H, W, D = C.shape
+    whole = L = C.clone()
+    if dy == 0:
+        C, L = C.transpose(0, 1), L.transpose(0, 1)            # views: columns as the leading axis, no column offset inside one
+        dy, dx, W = dx, 0, H
+    n = C.shape[0]
+    far = 1 << 20
+    lo, hi = max(dx, 0), W + min(dx, 0)                         # the positions of a line whose predecessor (at -dx) is inside
+    for i in (range(1, n) if dy > 0 else range(n - 2, -1, -1)):
+        prev = L[i - dy, lo - dx:hi - dx]
+        m = prev.min(dim=1, keepdim=True).values
+        side = TF.pad(prev, (1, 1), value=far)
+        best = torch.minimum(torch.minimum(prev, torch.minimum(side[:, :-2], side[:, 2:]) + p1), m + p2)
+        L[i, lo:hi] = C[i, lo:hi] + best - m
+    return whole
+
+
+def stereo_hints(target, partner, K, T, max_disp=64, p1=8, p2=64, return_volume=False):
+    """Stereo proxy depth in plain torch for CPU tensors (include/mdx.h "stereo proxy depth" has the definition, items 1-10;
+    mdx.functional.stereo_hints is the GPU form): census + semi-global matching over the rectified pair target / partner
+    [B,3,H,W], left-right checked.  -> dict(depth, disp float32 [B,1,H,W], 0 where invalid; valid uint8 [B,1,H,W]
+    [, volume = S uint16-valued int32 [B,H,W,D]]).  Integers as the definition states them, floats in its order."""
+    _notice()
+    if any(t.is_cuda for t in (target, partner, K, T)):
+        from ._lib import MdxError
+        raise MdxError("mdx.composite.stereo_hints is the CPU form: GPU tensors go to mdx.functional.stereo_hints")
+    D, p1, p2 = int(max_disp), int(p1), int(p2)
+    if D not in (64, 128) or not 0 < p1 < p2 <= 190 or target.dim() != 4 or target.shape[1] != 3 or partner.shape != target.shape:
+        raise ValueError("stereo_hints: max_disp %r (64 or 128), p1 %r < p2 %r <= 190, images %s / %s ([B,3,H,W])"
+                         % (max_disp, p1, p2, tuple(target.shape), tuple(partner.shape)))
+    B, _, H, W = target.shape
+    target, partner, K, T = target.float(), partner.float(), K.float(), T.float()
+    ys = torch.arange(H)
+    xs = torch.arange(W)
+
+    def census(img):
+        L = (0.299 * img[0] + 0.587 * img[1]) + 0.114 * img[2]
+        bits = [L[(ys + dy).clamp(0, H - 1)][:, (xs + dx).clamp(0, W - 1)] < L
+                for dy in range(-3, 4) for dx in range(-4, 5) if (dy, dx) != (0, 0)]
+        return torch.stack(bits, -1)
+
+    out = dict(depth=torch.zeros(B, 1, H, W), disp=torch.zeros(B, 1, H, W), valid=torch.zeros(B, 1, H, W, dtype=torch.uint8))
+    volume = torch.zeros(B, H, W, D, dtype=torch.int32)
+    for b in range(B):
+        tx = T[b, 0, 3]
+        if not bool(torch.isfinite(tx)) or float(tx) == 0:
+            continue
+        sgn = 1 if float(tx) > 0 else -1
+        ct, cs = census(target[b]), census(partner[b])
+        C = torch.full((H, W, D), 31, dtype=torch.int32)
+        for d in range(min(D, W)):
+            a, z = (0, W - d) if sgn > 0 else (d, W)              # the target columns whose match lies inside
+            C[:, a:z, d] = (ct[:, a:z] != cs[:, a + sgn * d:z + sgn * d]).sum(-1, dtype=torch.int32)
+        S = sum(_sgm_path(C, dy, dx, p1, p2) for dy, dx in ((0, 1), (0, -1), (1, 0), (-1, 0), (1, 1), (1, -1), (-1, 1), (-1, -1)))
+        volume[b] = S
+        key = S.long() * 256 + torch.arange(D)                    # the smallest S, then the smallest d
+        d0 = key.min(dim=2).values % 256
+        # the partner's view: column xr sees S(y, xr - sgn*d, d)
+        cols = xs[:, None] - sgn * torch.arange(D)[None, :]       # [W,D]
+        seen = torch.where(((cols >= 0) & (cols < W))[None], key[:, cols.clamp(0, W - 1), torch.arange(D)[None, :]],
+                           torch.full((), 1 << 40, dtype=torch.long))
+        dR = seen.min(dim=2).values % 256
+        xm = xs[None, :] + sgn * d0
+        inside = (xm >= 0) & (xm < W)
+        valid = (d0 >= 1) & inside & ((torch.gather(dR, 1, xm.clamp(0, W - 1)) - d0).abs() <= 1)
+        Sf = S.float()
+        a = torch.gather(Sf, 2, (d0 - 1).clamp(0, D - 1)[..., None])[..., 0]
+        m = torch.gather(Sf, 2, d0[..., None])[..., 0]
+        c = torch.gather(Sf, 2, (d0 + 1).clamp(0, D - 1)[..., None])[..., 0]
+        den = (a + c) - 2 * m
+        fit = (d0 > 0) & (d0 < D - 1) & (den > 0)
+        dsub = torch.where(fit, d0.float() + (a - c) / (2 * torch.where(fit, den, torch.ones_like(den))), d0.float())
+        num = K[b, 0, 0] * tx.abs()
+        out["disp"][b, 0] = torch.where(valid, dsub, torch.zeros_like(dsub))
+        out["depth"][b, 0] = torch.where(valid, num / torch.where(valid, dsub, torch.ones_like(dsub)), torch.zeros_like(dsub))
+        out["valid"][b, 0] = valid.to(torch.uint8)
+    if return_volume:
+        out["volume"] = volume
+    return out

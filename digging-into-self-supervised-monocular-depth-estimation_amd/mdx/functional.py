@@ -1419,3 +1419,52 @@ def sparse_depth_loss(disps, gt, min_depth, max_depth, lo=None, hi=None, eps=1e-
     out = _SparseDepth.apply(gt, cfg, *disps)
     n = len(disps)
     return dict(loss=out[:n], valid=out[n].detach())
+
+
+# ---- stereo proxy depth (csrc/stereo_hints.hip) -------------------------------------------------------------------------
+_hint_workspaces = {}                 # (device index, B, H, W, D) -> the workspace of that shape: allocated by the first call (the warm-up
+                                      # of a captured step), found there by every later one
+
+
+def stereo_hints_workspaces():
+    """The shapes for which stereo_hints() holds a workspace (none until it has been called)."""
+    return sorted(_hint_workspaces)
+
+
+def stereo_hints(target, partner, K, T, max_disp=64, p1=8, p2=64, return_volume=False):
+    """Stereo proxy depth (include/mdx.h "stereo proxy depth" has the definition, items 1-10; csrc/stereo_hints.hip): a census +
+    semi-global matcher over the rectified pair target / partner ([B,3,H,W]; the un-augmented ("color", 0, 0) and ("color", "s", 0)),
+    left-right checked, with K [B,4,4] (scale 0) and T = inputs["stereo"] [B,4,4] read on the device.
+    -> dict(depth, disp: float32 [B,1,H,W], 0 where invalid; valid: uint8 [B,1,H,W][, volume: S as int16 [B,H,W,D], a VIEW of the
+    workspace that the next call of this shape overwrites]).  No autograd: a function of the inputs alone.  12 launches, no
+    synchronisation, capturable, the same bits at every call; the workspace is kept per shape."""
+    D = int(max_disp)
+    tensors = (target, partner, K, T)
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise _lib.MdxError("stereo_hints: target, partner, K and T must be tensors")
+    if any(not t.is_cuda for t in tensors):
+        raise _lib.MdxError("stereo_hints: mdx kernels run on the GPU only (no CPU fallback); mdx.composite.stereo_hints takes CPU tensors")
+    if target.dim() != 4 or target.shape[1] != 3 or partner.shape != target.shape:
+        raise _lib.MdxError("stereo_hints: images of %s and %s, not one [B,3,H,W]" % (tuple(target.shape), tuple(partner.shape)))
+    B, _, H, W = (int(v) for v in target.shape)
+    if tuple(K.shape) != (B, 4, 4) or tuple(T.shape) != (B, 4, 4):
+        raise _lib.MdxError("stereo_hints: K %s and T %s, not [%d,4,4]" % (tuple(K.shape), tuple(T.shape), B))
+    with torch.no_grad():
+        target, partner, K, T = (_f32c(t.detach()) for t in tensors)
+        nws = api.mdx_stereo_hints_workspace_bytes(B, H, W, D)
+        if nws == 0:
+            raise _lib.MdxError("stereo_hints: sizes B %d, H %d, W %d, max_disp %d are not supported" % (B, H, W, D))
+        dev = target.device
+        key = (dev.index, B, H, W, D)
+        ws = _hint_workspaces.get(key)
+        if ws is None:
+            ws = _hint_workspaces[key] = workspace(nws, dev)
+        disp = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+        depth = torch.empty_like(disp)
+        valid = torch.empty(B, 1, H, W, device=dev, dtype=torch.uint8)
+        api.mdx_stereo_hints(ptr(target), ptr(partner), ptr(K), ptr(T), B, H, W, D, int(p1), int(p2), ptr(disp), ptr(depth),
+                             ptr(valid, torch.uint8), ptr(ws, torch.uint8), nws, stream())
+    out = dict(depth=depth, disp=disp, valid=valid)
+    if return_volume:
+        out["volume"] = ws[:B * H * W * D * 2].view(torch.int16).view(B, H, W, D)
+    return out

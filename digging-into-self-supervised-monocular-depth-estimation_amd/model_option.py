@@ -113,6 +113,21 @@ def options(argv=None):
                         "batch 12 at 192x640 under 375x1242 ground truth, 4.5 %% valid: forward + backward 265 us in 6 launches against 2016 us "
                         "in 200 launches for the same term in torch ops; the training loop's step -- the captured step and the five eager launches behind "
                         "it that keep the epoch's sums -- 14.66 -> 15.01 ms (+2.4 %%)")
+    p.add_argument("--stereo_hints", type=float, default=0.0,
+                   help="W > 0: proxy depth from the rectified stereo pair of the batch -- needs \"s\" in --frame_ids and inputs[\"stereo\"]: "
+                        "a census + semi-global matcher (9x7 census, eight paths, P1 8, P2 64, left-right check, sub-pixel parabola; "
+                        "csrc/stereo_hints.hip, include/mdx.h has the definition) over the un-augmented (\"color\", 0, 0) and "
+                        "(\"color\", \"s\", 0) gives depth = fx * baseline / disparity where the check holds, and W * the mean over the "
+                        "scales of the --depth_supervision penalty against it joins the loss (a second model_loss.SparseDepthLoss; "
+                        "may be on together with --depth_supervision).  On the device, inside the captured step, bit-reproducible.  A "
+                        "data-parallel run normalises by each rank's OWN valid count, so the exchanged gradient is the mean of the "
+                        "ranks' terms, not the term of the pooled batch.  Prints one line per epoch.  0: off, no module, no workspace, "
+                        "none of its kernels run.  No KITTI accuracy has been measured with it: the claim is that the hints are what "
+                        "the definition says.  Measured (tools/stereo_hints_cost.py, profiles/r16_stereo_hints_cost.txt, LABNOTES "
+                        "'Stereo proxy depth'): batch 12 at 192x640: the matcher 1.74 ms per call at 64 disparities (12 launches; its path passes move 2.83 GB, 0.35 ms at 8 TB/s: latency-bound walks), 3.71 ms at 128; the training loop's step at frame_ids 0 -1 1 s -- the captured step and the eager launches behind it that keep the epoch's sums -- 14.68 -> 16.85 ms (+14.8 %%)")
+    p.add_argument("--stereo_hints_disp", type=int, default=64, choices=[64, 128],
+                   help="--stereo_hints: the disparities searched.  At 640 columns fx * 0.1 = 37.1, so 64 reaches down to a depth of 0.58 "
+                        "units (about 3.1 m); nearer pixels fail the left-right check and get no hint")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

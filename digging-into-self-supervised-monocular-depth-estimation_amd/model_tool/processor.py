@@ -20,6 +20,7 @@ import torch
 
 from model_layer import *  # noqa: F401,F403  (the reference does the same star-import, processor.py:11)
 from model_loss import *   # noqa: F401,F403
+from mdx import composite
 from mdx import functional as F
 
 
@@ -96,6 +97,14 @@ class compute(object):
         # --depth_supervision W > 0: the sparse lidar term joins the loss of every path (_depth_term); 0: no loss module is made, none of its kernels run
         self.depth_supervision = float(_opt(opt, "depth_supervision", 0.0) or 0.0)
         self._depth_loss = None
+        # --stereo_hints W > 0: proxy depth from a semi-global matcher over the stereo pair joins the loss of every path (_hint_term);
+        # 0: no loss module is made, no workspace is held, none of its kernels run
+        self.stereo_hints = float(_opt(opt, "stereo_hints", 0.0) or 0.0)
+        self.stereo_hints_disp = int(_opt(opt, "stereo_hints_disp", 64) or 64)
+        self._hint_loss = None
+        if self.stereo_hints > 0 and "s" not in list(opt.frame_ids):
+            raise ValueError("--stereo_hints %g needs the stereo partner: \"s\" in --frame_ids (got %s)"
+                             % (self.stereo_hints, list(opt.frame_ids)))
 
     # -- networks ---------------------------------------------------------------------------------
     def _autocast(self):
@@ -371,6 +380,8 @@ class compute(object):
         outputs["loss"] = self.loss_path(target)(s, inputs, outputs, setting)
         if self.depth_supervision > 0:
             self._depth_term(s, inputs, outputs)
+        if self.stereo_hints > 0:
+            self._hint_term(s, inputs, outputs)
         return outputs
 
     def _depth_term(self, s, inputs, outputs):
@@ -388,6 +399,27 @@ class compute(object):
         outputs["loss_depth"] = res["loss"].detach()
         outputs["depth_valid"] = res["valid"]
         outputs["loss"] = outputs["loss"] + self.depth_supervision * res["loss"].mean()
+
+    def _hint_term(self, s, inputs, outputs):
+        """--stereo_hints W: W * mean_k L_k on top of whichever path formed outputs["loss"], L_k the sparse depth term of scale k
+        (a second model_loss.SparseDepthLoss) against the proxy depth of a semi-global matcher over the un-augmented stereo pair
+        (mdx.functional.stereo_hints: csrc/stereo_hints.hip for GPU tensors, mdx.composite.stereo_hints for CPU ones).  The hint is a
+        function of the inputs alone and is formed under no_grad; its invalid pixels are 0, which the term leaves out.  Nothing here
+        reads the host."""
+        T, partner, K = inputs.get("stereo"), inputs.get(("color", "s", 0)), inputs.get(("K", 0))
+        if not (torch.is_tensor(T) and torch.is_tensor(partner) and torch.is_tensor(K)):
+            raise ValueError("--stereo_hints %g needs the stereo partner (\"color\", \"s\", 0), its transform inputs[\"stereo\"] and "
+                             "(\"K\", 0) in every batch, and this one lacks %s" % (self.stereo_hints, ", ".join(
+                                 n for n, v in (("the partner", partner), ("inputs[\"stereo\"]", T), ("(\"K\", 0)", K)) if not torch.is_tensor(v))))
+        if self._hint_loss is None:
+            self._hint_loss = SparseDepthLoss(self.opt.min_depth, self.opt.max_depth)
+        with torch.no_grad():
+            fn = F.stereo_hints if s.target.is_cuda else composite.stereo_hints
+            hint = fn(s.target.float(), partner.float(), K.float(), T.float(), max_disp=self.stereo_hints_disp)
+        res = self._hint_loss(s.disps, hint["depth"])
+        outputs["loss_hint"] = res["loss"].detach()
+        outputs["hint_valid"] = res["valid"]
+        outputs["loss"] = outputs["loss"] + self.stereo_hints * res["loss"].mean()
 
     def _scalar_tail(self, s, setting, mean_min, smooth_all):
         """processor.py:208-217 around a path's mean_min(k, scale).  smooth_all: every scale's smoothness term

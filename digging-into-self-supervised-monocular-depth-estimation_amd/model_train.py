@@ -278,6 +278,8 @@ class trainer(object):
         self._loss_stat_passes, self._loss_stat_torch, self._loss_stat_steps, self._loss_stat_total = 0, 0, {}, 0
         # --depth_supervision: the epoch's sums of the term and of the valid pixels, kept on the device, and the steps behind them
         self._depth_acc, self._depth_steps = None, 0
+        # --stereo_hints: the same sums for the hint term
+        self._hint_acc, self._hint_steps = None, 0
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
         if torch.cuda.is_available():
@@ -543,6 +545,27 @@ class trainer(object):
         return ("depth supervision: weight %g, mean term %.6g, %.1f valid pixels per image over %d steps"
                 % (self.compute.depth_supervision, term / max(steps, 1), valid / max(steps * self.opt.batch, 1), steps))
 
+    def stereo_hints_add(self, outputs):
+        """--stereo_hints: the step's mean term and valid hint pixels join the epoch's sums where they are, on the device (float64);
+        nothing is read here.  Small eager launches behind every step, outside the captured graph, as depth_supervision_add's."""
+        term, valid = outputs["loss_hint"], outputs["hint_valid"]
+        if self._hint_acc is None:
+            self._hint_acc = torch.zeros(2, dtype=torch.float64, device=term.device)
+        self._hint_acc += torch.stack([term.mean().double(), valid.double()])
+        self._hint_steps += 1
+
+    def stereo_hints_report(self):
+        """-> the line rank 0 prints after an epoch: the mean of the hint term over the epoch's steps and the mean share of an image's
+        pixels that carried a hint, of THIS rank's batches.  The one read of the host of --stereo_hints; starts the sums again."""
+        steps = self._hint_steps
+        term, valid = self._hint_acc.tolist() if steps else (0.0, 0.0)
+        if steps:
+            self._hint_acc.zero_()
+        self._hint_steps = 0
+        pixels = steps * self.opt.batch * self.opt.height * self.opt.width
+        return ("stereo hints: weight %g, %d disparities, mean term %.6g, valid share %.4f per image over %d steps"
+                % (self.compute.stereo_hints, self.compute.stereo_hints_disp, term / max(steps, 1), valid / max(pixels, 1), steps))
+
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise
         (--noise cpu: torch.randn on the CPU + a copy from pageable memory), not with a non-RCCL process group.  With more than
@@ -605,6 +628,7 @@ class trainer(object):
         # report covers rank 0's own batches
         loss_every = int(getattr(self.opt, "loss_stats", 0) or 0) if "loss_stats" in self.setting.optim else 0
         supervised = self.compute.depth_supervision > 0      # --depth_supervision: one line per epoch, read once per epoch
+        hinted = self.compute.stereo_hints > 0               # --stereo_hints: likewise
         for epoch in range(start, self.opt.epoch):
             batch_train = {k: [] for k in names}
             batch_valid = {k: [] for k in names}
@@ -624,6 +648,8 @@ class trainer(object):
                     self.loss_stats(train_outputs, done)
                 if supervised:
                     self.depth_supervision_add(train_outputs)
+                if hinted:
+                    self.stereo_hints_add(train_outputs)
                 if self.opt.max_steps and step + 1 >= self.opt.max_steps:
                     break
             self.setting.set_valid()
@@ -649,10 +675,13 @@ class trainer(object):
                 epoch_train[key].append(mean_train[key])
                 epoch_valid[key].append(mean_valid[key])
             depth_line = self.depth_supervision_report() if supervised else None
+            hint_line = self.stereo_hints_report() if hinted else None
             if self.rank == 0:
                 self.control.print(epoch, mean_train, mean_valid)
                 if depth_line:
                     print(depth_line, flush=True)
+                if hint_line:
+                    print(hint_line, flush=True)
                 optimizer = self.setting.optim["optimizer"]
                 if getattr(optimizer, "guarded", False):
                     g = optimizer.guard_stats()

@@ -781,6 +781,36 @@ int mdx_sparse_depth_bwd(int nscales, int B, const int *h, const int *w, const f
                          double min_depth, double max_depth, float lo, float hi, double eps, const float *out, const float *gout,
                          float *const *ddisp, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- stereo proxy depth: a semi-global matcher over a rectified pair (csrc/stereo_hints.hip; mdx.functional.stereo_hints).
+ * target, partner: float32 contiguous [B,3,H,W]; K, T: float32 [B,4,4] (scale-0 intrinsics; the target -> partner transform, the
+ * loaders' inputs["stereo"]), read on the device; D = 64 or 128 disparities; integers 0 < P1 < P2 <= 190.  Per sample b:
+ *  1. dir = +1 if T[b,0,3] > 0, -1 if < 0: the match of target (y,x) at disparity d is partner (y, x + dir*d).  T[b,0,3] zero or not
+ *     finite: the sample's S, disp, depth and valid are all 0.
+ *  2. luma  L = (0.299f*R + 0.587f*G) + 0.114f*B in float32, each operation rounded on its own.
+ *  3. census over 9 wide x 7 high: 62 bits, bit = L(neighbour) < L(centre), neighbour coordinates clamped to the image.
+ *  4. cost  C(y,x,d) = popcount(ct(y,x) ^ cs(y,x+dir*d)) if 0 <= x+dir*d < W, else 31.
+ *  5. paths r in {(0,+-1), (+-1,0), (+-1,+-1)} as (row, column) steps: L_r(p,d) = C(p,d) where p-r lies outside the image, else
+ *     C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1)+P1, L_r(p-r,d+1)+P1, m+P2) - m with m = min_k L_r(p-r,k); the d-1 / d+1 terms are
+ *     absent at d = 0 / d = D-1.  S = sum_r L_r (L_r <= 62+P2 <= 252, S <= 2016: 16 bits).
+ *  6. d0(p) = argmin_d S(p,d), the smallest d on ties.
+ *  7. dR(y,xr) = argmin_d S(y, xr - dir*d, d) over the d whose column lies inside the image, the smallest d on ties.
+ *  8. valid: d0 >= 1 and 0 <= x+dir*d0 < W and |dR(y, x+dir*d0) - d0| <= 1.
+ *  9. in float32: a = S(p,d0-1), m = S(p,d0), c = S(p,d0+1), den = (a + c) - 2*m; if 0 < d0 < D-1 and den > 0:
+ *     dsub = d0 + (a - c) / (2*den), else dsub = d0.
+ * 10. disp[b,0,y,x] = dsub where valid, else 0; depth = (K[b,0,0] * |T[b,0,3]|) / dsub where valid (the product first, the quotient
+ *     correctly rounded), else 0; valid[b,0,y,x] = 1 / 0 (uint8).  Every element of the three outputs is written.
+ * Workspace (mdx_stereo_hints_workspace_bytes; 0 for sizes the call refuses; 8-byte aligned): S lies at offset 0 as uint16
+ * [B][H][W][D]; behind it, each rounded up to 8 bytes, the two census maps (uint64 [B][H][W], target then partner), the two luma maps
+ * (float32 [B][H][W]), d0 and dR (uint8 [B][H][W]).  It may hold anything on entry: the first path pass writes S, the other seven
+ * add to it, each element with one writer per launch.  12 launches (luma, census, 8 paths, the two winners, outputs), no
+ * atomics, no host synchronisation (capturable); the same inputs give the same bits at every call.
+ * Refusals, all before anything is launched, in this order: MDX_ERR_NULL_POINTER (target, partner, K, T, disp, depth, valid);
+ * MDX_ERR_BAD_SHAPE (B, H or W < 1, H or W > 32767, D not 64 / 128, B*H*W*D >= 2^31, !(0 < P1 < P2 <= 190)); MDX_ERR_WORKSPACE
+ * (NULL or too small); MDX_ERR_MISALIGNED (a float pointer not 4-byte, the workspace not 8-byte aligned). */
+size_t mdx_stereo_hints_workspace_bytes(int B, int H, int W, int D);
+int mdx_stereo_hints(const float *target, const float *partner, const float *K, const float *T, int B, int H, int W, int D, int P1,
+                     int P2, float *disp, float *depth, unsigned char *valid, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
