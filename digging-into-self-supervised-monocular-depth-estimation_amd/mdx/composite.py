@@ -204,3 +204,30 @@ def stereo_hints(target, partner, K, T, max_disp=64, p1=8, p2=64, return_volume=
     if return_volume:
         out["volume"] = volume
     return out
+
+
+def hint_select(target, partner, K, invK, T, hint, disp, min_depth, max_depth, return_losses=False):
+    """Depth-hint selection in plain torch for CPU tensors (include/mdx.h "depth-hint selection" has the definition;
+    mdx.functional.hint_select is the GPU form), from the ops above: the hint ([B,1,H,W], 0 = none) is kept only where the partner
+    warped with it gives a strictly lower reprojection loss against `target` than the partner warped with the depth of `disp`
+    ([B,1,h,w]).  -> dict(sel float32 [B,1,H,W], counts int32 [B,2] = (hints, kept)[, l_hint, l_pred])."""
+    _notice()
+    tensors = (target, partner, K, invK, T, hint, disp)
+    if any(t.is_cuda for t in tensors):
+        from ._lib import MdxError
+        raise MdxError("mdx.composite.hint_select is the CPU form: GPU tensors go to mdx.functional.hint_select")
+    with torch.no_grad():
+        target, partner, K, invK, T, hint, disp = (t.detach().float() for t in tensors)
+        B, _, H, W = target.shape
+        if tuple(hint.shape) != (B, 1, H, W) or disp.dim() != 4 or disp.shape[2] > H or disp.shape[3] > W:
+            raise ValueError("hint_select: hint %s and disp %s against images of %s" % (tuple(hint.shape), tuple(disp.shape), tuple(target.shape)))
+        up = disp if tuple(disp.shape[2:]) == (H, W) else interpolate_bilinear(disp, H, W)
+        losses = [reprojection_loss(grid_sample_border(partner, project(backproject(d, invK), K, T, H, W)), target)
+                  for d in (hint, disparity2depth(up, min_depth, max_depth)[1])]
+        has = hint > 0
+        keep = has & (losses[0] < losses[1])
+        out = dict(sel=torch.where(keep, hint, torch.zeros_like(hint)),
+                   counts=torch.stack([has.sum((1, 2, 3)), keep.sum((1, 2, 3))], 1).to(torch.int32))
+        if return_losses:
+            out["l_hint"], out["l_pred"] = losses
+    return out

@@ -1468,3 +1468,60 @@ def stereo_hints(target, partner, K, T, max_disp=64, p1=8, p2=64, return_volume=
     if return_volume:
         out["volume"] = ws[:B * H * W * D * 2].view(torch.int16).view(B, H, W, D)
     return out
+
+
+# ---- depth-hint selection (csrc/hint_select.hip) ---------------------------------------------------------------------------
+_select_workspaces = {}               # (device index, B, H, W, h, w) -> the workspace of that shape, as _hint_workspaces
+
+
+def hint_select_workspaces():
+    """The shapes for which hint_select() holds a workspace (none until it has been called)."""
+    return sorted(_select_workspaces)
+
+
+def hint_select(target, partner, K, invK, T, hint, disp, min_depth, max_depth, return_losses=False):
+    """Depth-hint selection (include/mdx.h "depth-hint selection" has the definition; csrc/hint_select.hip): the hint ([B,1,H,W], 0 =
+    none) is kept at a pixel only where the partner warped with it gives a strictly lower ReprojectionLoss against `target` than
+    the partner warped with the depth of `disp` ([B,1,h,w], the step's finest disparity: upsampled, then disparity2depth).
+    -> dict(sel: float32 [B,1,H,W], the hint where kept and 0 elsewhere; counts: int32 [B,2] = (hints, kept)
+    [, l_hint, l_pred: float32 [B,1,H,W]]).  Runs under no_grad, nothing is differentiable.  Two launches, no synchronisation,
+    capturable, the same bits at every call; the workspace is kept per shape."""
+    tensors = (target, partner, K, invK, T, hint, disp)
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise _lib.MdxError("hint_select: target, partner, K, invK, T, hint and disp must be tensors")
+    if any(not t.is_cuda for t in tensors):
+        raise _lib.MdxError("hint_select: mdx kernels run on the GPU only (no CPU fallback); mdx.composite.hint_select takes CPU tensors")
+    if target.dim() != 4 or target.shape[1] != 3 or partner.shape != target.shape:
+        raise _lib.MdxError("hint_select: images of %s and %s, not one [B,3,H,W]" % (tuple(target.shape), tuple(partner.shape)))
+    B, _, H, W = (int(v) for v in target.shape)
+    if any(tuple(m.shape) != (B, 4, 4) for m in (K, invK, T)):
+        raise _lib.MdxError("hint_select: K %s, invK %s and T %s, not [%d,4,4]" % (tuple(K.shape), tuple(invK.shape), tuple(T.shape), B))
+    if tuple(hint.shape) != (B, 1, H, W) or disp.dim() != 4 or tuple(disp.shape[:2]) != (B, 1):
+        raise _lib.MdxError("hint_select: hint %s, not [%d,1,%d,%d], or disp %s, not [%d,1,h,w]"
+                            % (tuple(hint.shape), B, H, W, tuple(disp.shape), B))
+    h, w = int(disp.shape[2]), int(disp.shape[3])
+    min_depth, max_depth = float(min_depth), float(max_depth)
+    with torch.no_grad():
+        target, partner, K, invK, T, hint, disp = (_f32c(t.detach()) for t in tensors)
+        if target.data_ptr() % 16:                 # a view into a larger buffer: the kernel reads the target's planes with 16-byte loads
+            target = target.clone()
+        nws = api.mdx_hint_select_workspace_bytes(B, H, W, h, w)
+        if nws == 0 or not (min_depth > 0 and max_depth > min_depth):
+            raise _lib.MdxError("hint_select: sizes B %d, H %d, W %d, disp %d x %d, depths %r..%r are not supported"
+                                % (B, H, W, h, w, min_depth, max_depth))
+        dev = target.device
+        key = (dev.index, B, H, W, h, w)
+        ws = _select_workspaces.get(key)
+        if ws is None:
+            ws = _select_workspaces[key] = workspace(nws, dev)
+        sel = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+        counts = torch.empty(B, 2, device=dev, dtype=torch.int32)
+        lh = torch.empty_like(sel) if return_losses else None
+        lp = torch.empty_like(sel) if return_losses else None
+        api.mdx_hint_select(ptr(target), ptr(partner), ptr(K), ptr(invK), ptr(T), ptr(hint), ptr(disp), B, H, W, h, w, min_depth,
+                            max_depth, ptr(sel), ptr(lh, optional=True), ptr(lp, optional=True), ptr(counts, torch.int32),
+                            ptr(ws, torch.uint8), nws, stream())
+    out = dict(sel=sel, counts=counts)
+    if return_losses:
+        out["l_hint"], out["l_pred"] = lh, lp
+    return out

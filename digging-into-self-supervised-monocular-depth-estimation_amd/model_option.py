@@ -128,6 +128,15 @@ def options(argv=None):
     p.add_argument("--stereo_hints_disp", type=int, default=64, choices=[64, 128],
                    help="--stereo_hints: the disparities searched.  At 640 columns fx * 0.1 = 37.1, so 64 reaches down to a depth of 0.58 "
                         "units (about 3.1 m); nearer pixels fail the left-right check and get no hint")
+    p.add_argument("--stereo_hints_select", action="store_true",
+                   help="--stereo_hints W > 0 only (it means nothing without it): a hint supervises a pixel only where warping the stereo "
+                        "partner with the hint depth gives a strictly lower SSIM + L1 reprojection loss against the target than warping it "
+                        "with the depth of the step's own finest disparity (the rule of Watson et al. 2019 through the stereo view alone, "
+                        "not the minimum over all sources; include/mdx.h 'depth-hint selection', csrc/hint_select.hip, DESIGN.md 4.7); "
+                        "the selected map goes to the same term, the epoch line carries the kept share.  Default off: no call, no "
+                        "workspace.  No KITTI accuracy has been measured with it.  Measured (tools/hint_select_cost.py, profiles/r17_hint_select_cost.txt, LABNOTES "
+                        "'Depth-hint selection'): batch 12 at 192x640: 0.047 ms per call in 2 launches against 0.199 ms in about 17 for the same result from "
+                        "the fine-grained ops; the training loop's step at frame_ids 0 -1 1 s with --stereo_hints 0.05 16.90 -> 16.97 ms (+0.44 %%)")
     p.add_argument("--shadow_weights", type=int, default=1,
                    help="--amp bf16: cast every convolution weight once per step by one launch (mdx/shadow.py); 0: autocast's cast per convolution")
     p.add_argument("--fused_tail", type=int, default=1,

@@ -102,6 +102,8 @@ class compute(object):
         self.stereo_hints = float(_opt(opt, "stereo_hints", 0.0) or 0.0)
         self.stereo_hints_disp = int(_opt(opt, "stereo_hints_disp", 64) or 64)
         self._hint_loss = None
+        # --stereo_hints_select: the hints pass the reprojection test first (_hint_term); means nothing while --stereo_hints is 0
+        self.stereo_hints_select = bool(_opt(opt, "stereo_hints_select", False)) and self.stereo_hints > 0
         if self.stereo_hints > 0 and "s" not in list(opt.frame_ids):
             raise ValueError("--stereo_hints %g needs the stereo partner: \"s\" in --frame_ids (got %s)"
                              % (self.stereo_hints, list(opt.frame_ids)))
@@ -404,7 +406,8 @@ class compute(object):
         """--stereo_hints W: W * mean_k L_k on top of whichever path formed outputs["loss"], L_k the sparse depth term of scale k
         (a second model_loss.SparseDepthLoss) against the proxy depth of a semi-global matcher over the un-augmented stereo pair
         (mdx.functional.stereo_hints: csrc/stereo_hints.hip for GPU tensors, mdx.composite.stereo_hints for CPU ones).  The hint is a
-        function of the inputs alone and is formed under no_grad; its invalid pixels are 0, which the term leaves out.  Nothing here
+        function of the inputs alone and is formed under no_grad; its invalid pixels are 0, which the term leaves out.  With
+        --stereo_hints_select the map handed to the term is the selected one and outputs["hint_kept"] the kept count.  Nothing here
         reads the host."""
         T, partner, K = inputs.get("stereo"), inputs.get(("color", "s", 0)), inputs.get(("K", 0))
         if not (torch.is_tensor(T) and torch.is_tensor(partner) and torch.is_tensor(K)):
@@ -416,9 +419,24 @@ class compute(object):
         with torch.no_grad():
             fn = F.stereo_hints if s.target.is_cuda else composite.stereo_hints
             hint = fn(s.target.float(), partner.float(), K.float(), T.float(), max_disp=self.stereo_hints_disp)
-        res = self._hint_loss(s.disps, hint["depth"])
+        depth, counts = hint["depth"], None
+        if self.stereo_hints_select:
+            # --stereo_hints_select: a hint supervises a pixel only where warping the partner with it reprojects better than warping it
+            # with the step's own finest depth (mdx.functional.hint_select: csrc/hint_select.hip; mdx.composite.hint_select on the CPU)
+            invK = inputs.get(("inv_K", 0))
+            if not torch.is_tensor(invK):
+                raise ValueError("--stereo_hints_select needs (\"inv_K\", 0) in every batch, and this one has none")
+            with torch.no_grad():
+                fn = F.hint_select if s.target.is_cuda else composite.hint_select
+                picked = fn(s.target.float(), partner.float(), K.float(), invK.float(), T.float(), depth, s.disps[0].detach(),
+                            self.opt.min_depth, self.opt.max_depth)
+            depth, counts = picked["sel"], picked["counts"].sum(0).to(torch.float32)
+        res = self._hint_loss(s.disps, depth)
         outputs["loss_hint"] = res["loss"].detach()
-        outputs["hint_valid"] = res["valid"]
+        # the hints of the batch: those the term counts (inside the depth range), or with the selection on every hint > 0, the kept beside them
+        outputs["hint_valid"] = res["valid"] if counts is None else counts[0]
+        if counts is not None:
+            outputs["hint_kept"] = counts[1]
         outputs["loss"] = outputs["loss"] + self.stereo_hints * res["loss"].mean()
 
     def _scalar_tail(self, s, setting, mean_min, smooth_all):

@@ -549,22 +549,28 @@ class trainer(object):
         """--stereo_hints: the step's mean term and valid hint pixels join the epoch's sums where they are, on the device (float64);
         nothing is read here.  Small eager launches behind every step, outside the captured graph, as depth_supervision_add's."""
         term, valid = outputs["loss_hint"], outputs["hint_valid"]
+        sums = [term.mean().double(), valid.double()]
+        if "hint_kept" in outputs:                       # --stereo_hints_select: the kept hints beside them
+            sums.append(outputs["hint_kept"].double())
         if self._hint_acc is None:
-            self._hint_acc = torch.zeros(2, dtype=torch.float64, device=term.device)
-        self._hint_acc += torch.stack([term.mean().double(), valid.double()])
+            self._hint_acc = torch.zeros(len(sums), dtype=torch.float64, device=term.device)
+        self._hint_acc += torch.stack(sums)
         self._hint_steps += 1
 
     def stereo_hints_report(self):
         """-> the line rank 0 prints after an epoch: the mean of the hint term over the epoch's steps and the mean share of an image's
         pixels that carried a hint, of THIS rank's batches.  The one read of the host of --stereo_hints; starts the sums again."""
         steps = self._hint_steps
-        term, valid = self._hint_acc.tolist() if steps else (0.0, 0.0)
+        term, valid, *kept = self._hint_acc.tolist() if steps else (0.0, 0.0)
         if steps:
             self._hint_acc.zero_()
         self._hint_steps = 0
         pixels = steps * self.opt.batch * self.opt.height * self.opt.width
-        return ("stereo hints: weight %g, %d disparities, mean term %.6g, valid share %.4f per image over %d steps"
+        line = ("stereo hints: weight %g, %d disparities, mean term %.6g, valid share %.4f per image over %d steps"
                 % (self.compute.stereo_hints, self.compute.stereo_hints_disp, term / max(steps, 1), valid / max(pixels, 1), steps))
+        if kept:                                         # --stereo_hints_select: the share of the hints that passed the reprojection test
+            line += ", kept share %.4f of the hints" % (kept[0] / max(valid, 1.0))
+        return line
 
     def can_graph(self):
         """The step is capturable when nothing in it runs on the host: not with the reference's host-side noise

@@ -811,6 +811,41 @@ size_t mdx_stereo_hints_workspace_bytes(int B, int H, int W, int D);
 int mdx_stereo_hints(const float *target, const float *partner, const float *K, const float *T, int B, int H, int W, int D, int P1,
                      int P2, float *disp, float *depth, unsigned char *valid, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- depth-hint selection: a proxy depth supervises a pixel only where it reprojects better than the network's own depth
+ * (Watson et al. 2019; csrc/hint_select.hip; mdx.functional.hint_select, mdx.composite.hint_select).
+ * target, partner: float32 contiguous [B,3,H,W]; K, invK, T: float32 [B,4,4] (scale-0 intrinsics, their inverse, the target ->
+ * partner transform), read on the device; hint: float32 [B,1,H,W], 0 = no hint; disp: float32 [B,1,h,w], the step's finest
+ * disparity, h <= H, w <= W.  Per pixel (b,y,x):
+ *  1. u = the bilinear sample of disp at (y,x) on the H x W grid, align_corners=False (the element itself when the sizes are equal);
+ *     d_pred = 1 / (a + b*u) with a = 1/max_depth, b = 1/min_depth - 1/max_depth as mdx_disparity2depth_fwd forms them.
+ *  2. ray = invK[b,:3,:3] . (x, y, 1); P = (K[b] @ T[b])[:3] as mdx_compose_projection forms it.
+ *  3. for d in (hint, d_pred): the point (d*ray, 1) through mdx_project_fwd's arithmetic (eps 1e-7) to a sampling position, the
+ *     three partner planes sampled there as mdx_grid_sample_border_fwd samples them (bilinear, border, align_corners=True).  This
+ *     is done over the whole map as given: a 0 (or any other value) in hint is warped like a depth.
+ *  4. l_hint, l_pred = mdx_reprojection_loss_fwd of the two warped images against target: 0.85 * the channel mean of the clamped
+ *     SSIM map (3 x 3 windows, reflect padding: a window position outside the image is the reflected position inside it, warped
+ *     there) + 0.15 * the channel mean of |target - warped|.
+ *  5. keep = hint > 0 && l_hint < l_pred.  Strict: a tie keeps nothing; a comparison with a NaN is false.
+ *  6. sel[b,0,y,x] = keep ? hint : 0 (the hint's own bits); l_hint / l_pred [B,1,H,W] are written when the pointers are not NULL.
+ *  7. counts[b] = (the pixels with hint > 0, the pixels kept) as int32 [B][2].
+ * Every float is formed in the order of the calls named above, so l_hint and l_pred equal their chain bit for bit.  Where a
+ * non-finite value of hint or of the upsampled disparity lies inside a pixel's 3 x 3 window that pixel's keep is unspecified (sel is
+ * still 0 or the hint); every pixel farther away is unaffected.  No index is formed from an unclamped float: sampling positions are
+ * clamped to the image (a NaN to 0) before they are converted.
+ * Two launches (one 64 x 8 tile per block with its halo in LDS; one block per sample adds the tiles' integer counts), no atomics,
+ * every output element written by one plain store, no host synchronisation (capturable); the same inputs give the same bits at
+ * every call.  Workspace (mdx_hint_select_workspace_bytes; 0 for sizes the call refuses; 8-byte aligned): one int32 pair per tile;
+ * it may hold anything on entry.
+ * Refusals, all before anything is launched, in this order: MDX_ERR_NULL_POINTER (target, partner, K, invK, T, hint, disp, sel,
+ * counts); MDX_ERR_BAD_SHAPE (B, h or w < 1, H or W < 2, h > H, w > W, H*W >= 2^30, B*H*W >= 2^31, B or ceil(H/8) > 65535,
+ * min_depth <= 0, max_depth <= min_depth); MDX_ERR_WORKSPACE (NULL or too small); MDX_ERR_MISALIGNED (a float or count pointer not
+ * 4-byte, the workspace not 8-byte, target not 16-byte aligned: its planes are read with 16-byte loads, and H*W*4 is a multiple of 16
+ * wherever those loads are taken, W % 4 == 0). */
+size_t mdx_hint_select_workspace_bytes(int B, int H, int W, int h, int w);
+int mdx_hint_select(const float *target, const float *partner, const float *K, const float *invK, const float *T, const float *hint,
+                    const float *disp, int B, int H, int W, int h, int w, double min_depth, double max_depth, float *sel,
+                    float *l_hint, float *l_pred, int *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
