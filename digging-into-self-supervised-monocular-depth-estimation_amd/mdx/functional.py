@@ -946,6 +946,55 @@ def thin_conv3x3(x, weight):
     return _ThinConv3x3.apply(x, weight)
 
 
+class _UpConv3x3(torch.autograd.Function):
+    """conv2d(ReflectionPad2d(1)(nearest_x2(ELU(raw + bias))), weight) on the low-resolution map (csrc/upconv_nhwc.hip)."""
+
+    @staticmethod
+    def forward(ctx, raw, bias, weight):
+        B, _, h, w = raw.shape
+        out = torch.empty(B, 16, 2 * h, 2 * w, device=raw.device, dtype=torch.float32, memory_format=_CL)
+        so, sc, sy, sx = weight.stride()
+        api.mdx_up_conv3x3_fwd(ptr(raw, cl=True), ptr(bias), ptr(weight, cl="any"), so, sc, sy, sx, ptr(out, cl=True), B, h, w, stream())
+        ctx.save_for_backward(raw, bias, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        raw, bias, weight = ctx.saved_tensors
+        B, _, h, w = raw.shape
+        gy = _as(gy, True)
+        graw, gbias, gw = torch.empty_like(raw), torch.empty_like(bias), torch.empty_like(weight)      # gw: the weight's own strides
+        nws = api.mdx_up_conv3x3_workspace_bytes(B, h, w)
+        ws = workspace(nws, raw.device)
+        so, sc, sy, sx = weight.stride()
+        go, gc, gy_, gx = gw.stride()
+        api.mdx_up_conv3x3_bwd(ptr(gy, cl=True), ptr(raw, cl=True), ptr(bias), ptr(weight, cl="any"), so, sc, sy, sx,
+                               ptr(graw, cl=True), ptr(gbias), ptr(gw, cl="any"), go, gc, gy_, gx, B, h, w, ptr(ws, torch.uint8), nws,
+                               stream())
+        return graw, gbias, gw
+
+
+def up_conv_ok(raw, weight):
+    """A stage up_conv3x3 takes: float32 channels-last GPU map [B,16,h,w] with w a multiple of 4, weight [16,16,3,3] (float32, dense,
+    either memory format), no autocast."""
+    return (_cl_map(raw, (torch.float32,)) and raw.shape[1] == 16 and raw.shape[3] % 4 == 0 and raw.shape[0] * raw.shape[2] > 0
+            and weight.is_cuda and weight.dtype == torch.float32 and tuple(weight.shape) == (16, 16, 3, 3)
+            and (weight.is_contiguous() or weight.is_contiguous(memory_format=_CL)) and not torch.is_autocast_enabled())
+
+
+def up_conv3x3(raw, bias, weight):
+    """conv2d(ReflectionPad2d(1)(nearest_x2(ELU(raw + bias))), weight), no output bias, for the decoder's last stage
+    (depth_decoder.py:96-106, the one stage convolution without a skip): raw [B,16,h,w] the previous convolution's output before
+    its bias and ELU, bias [16] that convolution's bias, weight [16,16,3,3] -> [B,16,2h,2w] channels-last.  decoder_glue(...,
+    bias=)'s convention.  Each output phase is a 2x2 convolution of the low-resolution map (csrc/upconv_nhwc.hip): the padded x2
+    copy and its gradient are never written; one launch forward, three backward."""
+    if not up_conv_ok(raw, weight) or not (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == torch.float32
+                                           and tuple(bias.shape) == (16,)):
+        raise _lib.MdxError("up_conv3x3: needs a float32 channels-last GPU map [B,16,h,w] with w %% 4 == 0, a float32 bias [16] and a "
+                            "float32 weight [16,16,3,3]; got raw %s %s, weight %s %s" % (tuple(raw.shape), raw.dtype, tuple(weight.shape), weight.dtype))
+    return _UpConv3x3.apply(raw, bias, weight)
+
+
 class _DispHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):

@@ -3,8 +3,13 @@
 Five stages, deepest first; stage i = ConvBlock -> nearest x2 -> concat encoder skip (i > 0) -> ConvBlock, and a
 sigmoid disparity head on the stages listed in `scales`.  The parameter names are the reference's
 (`decoder.<n>.conv.conv.{weight,bias}`, n in the reference's ModuleList order: the ten stage blocks from stage 4
-down to stage 0, then one head per scale), so checkpoints are interchangeable.  Convolutions run on MIOpen.
+down to stage 0, then one head per scale), so checkpoints are interchangeable.  Convolutions run on MIOpen, with one exception:
+stage 0's second convolution, the only one whose input is nothing but the x2 copy of a smaller map (no skip), runs on that smaller
+map as four 2x2 phase convolutions (mdx.functional.up_conv3x3, csrc/upconv_nhwc.hip) when it is a float32 channels-last 16 -> 16
+stage; `DepthDecoder.fused_upconv = False` or MDX_FUSED_UPCONV=0 in the environment give the MIOpen form back.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -40,6 +45,7 @@ class ConvBlock(nn.Module):
 class DepthDecoder(nn.Module):
     fused_heads = True          # False: the heads as MIOpen convolution + bias + sigmoid (A/B, parity tests)
     thin_wgrad = True           # False: MIOpen's weight gradient for the 16-channel stage convolutions too
+    fused_upconv = True         # False: stage 0's second convolution as glue (ELU, x2, pad) + MIOpen on the full-resolution map
 
     def __init__(self, num_ch_enc, scales=range(4), num_output_channels=1, use_skips=True):
         super().__init__()
@@ -103,7 +109,12 @@ class DepthDecoder(nn.Module):
             first, second = self._stage[i]
             raw, bias = conv(self.decoder[first], padded)
             skip = input_features[i - 1] if (self.use_skips and i > 0) else None
-            raw, bias = conv(self.decoder[second], F.decoder_glue(raw, skip, elu=True, upsample=True, bias=bias))
+            w2 = self.decoder[second].conv.conv.weight
+            if skip is None and self.fused_upconv and os.environ.get("MDX_FUSED_UPCONV", "1") != "0" and F.up_conv_ok(raw, w2):
+                # no skip: the convolution's input is a 4x replicated copy, never written (csrc/upconv_nhwc.hip)
+                raw, bias = F.up_conv3x3(raw, bias, w2), self.decoder[second].conv.conv.bias
+            else:
+                raw, bias = conv(self.decoder[second], F.decoder_glue(raw, skip, elu=True, upsample=True, bias=bias))
             padded = F.decoder_glue(raw, None, elu=True, upsample=False, bias=bias) if i > 0 else None
             if i in self._head:
                 head = self.decoder[self._head[i]].conv

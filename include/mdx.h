@@ -615,6 +615,23 @@ size_t mdx_thin_conv3x3_wgrad_workspace_bytes(int B, int Cin, int Cout, int h, i
 int mdx_thin_conv3x3_wgrad(const float *x, const float *gy, float *gweight, int64_t s_o, int64_t s_c, int64_t s_y, int64_t s_x, int B,
                            int Cin, int Cout, int h, int w, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The decoder's last stage convolution on the low-resolution map (csrc/upconv_nhwc.hip; mdx.functional.up_conv3x3):
+ *   out = conv3x3(ReflectionPad2d(1)(nearest_x2(ELU(raw + bias))), weight)          (no output bias)
+ * raw, graw [B][h][w][16], out, gy [B][2h][2w][16], float32 channels-last, 16-byte aligned; bias, gbias [16]; weight and gweight
+ * [16][16][3][3], element (co, ci, ky, kx) at [co * s_o + ci * s_c + ky * s_y + kx * s_x], each with its own strides.  Every output
+ * phase (2Y+py, 2X+px) is a 2x2 convolution of the low-resolution map with pre-summed taps and a clamped index: neither the padded
+ * x2 copy nor its gradient exists.  Forward one launch; backward three (data gradient with d(bias) partials, weight-gradient
+ * partials, one finishing pass in a fixed order), no atomics: the same inputs give the same bits at every call; no host
+ * synchronisation (capturable).  The workspace (mdx_up_conv3x3_workspace_bytes; 0 for sizes the calls refuse; 16-byte aligned) may
+ * hold anything on entry.  Refusals, before anything is launched: MDX_ERR_NULL_POINTER; MDX_ERR_BAD_SHAPE (B or h < 1, w not a
+ * positive multiple of 4, B*h*w >= 2^34); MDX_ERR_WORKSPACE; MDX_ERR_MISALIGNED. */
+size_t mdx_up_conv3x3_workspace_bytes(int B, int h, int w);
+int mdx_up_conv3x3_fwd(const float *raw, const float *bias, const float *weight, int64_t s_o, int64_t s_c, int64_t s_y, int64_t s_x,
+                       float *out, int B, int h, int w, void *stream);
+int mdx_up_conv3x3_bwd(const float *gy, const float *raw, const float *bias, const float *weight, int64_t s_o, int64_t s_c,
+                       int64_t s_y, int64_t s_x, float *graw, float *gbias, float *gweight, int64_t g_o, int64_t g_c, int64_t g_y,
+                       int64_t g_x, int B, int h, int w, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The decoder's disparity heads   model_layer/depth_decoder.py:73-74,108-110: sigmoid(Conv3x3(C -> 1)(x)) on a channels-last map.
  * x [B][h+2][w+2][C] = the reflection-padded input (mdx_decoder_glue_nhwc_fwd's output), dtype 0 float32 / 1 bfloat16, C a
  * power of two from 4 to 256; weight: float32, element (c, ky, kx) at
